@@ -12,12 +12,19 @@ the sample queue's tiles stay compact, and the sky-heavy top rows spread evenly)
 for all frames, then one RCCL gather over xGMI assembles the full image on rank 0 (inside the timed region).
 Total work is fixed as N grows -> "scaling": "strong"; `value` is the whole-job rate.
 
-Single-GPU proxy of that split (`--emulate-ranks N`, default 8 on a one-rank run): after the timed region,
-every rank's share is rendered on this GPU in turn with the same step; the predicted N-GPU step time is the
-slowest share's, and `emulated_split.efficiency` = full-image time / (N x slowest share).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints ONE JSON line on
+rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall milliseconds of one timed step), the
+workload's `config`, and `roofline` (FP32-VALU bound; HIP-event time of the render kernel on the stream it runs on),
+worked out from the timed steps' own statistics and the box / sphere test counts of the warmup steps (no warmup: no
+counts, and a plain line leaves the block out). `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs below).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), plus `roofline` (FP32-VALU bound; HIP-event
-time of the render kernel on the stream it runs on) and `cpu_baseline` (the CPU oracle on a bounded sample).
+`--full` adds what takes runs of its own, after the timed region: the counting draw for `roofline` when there was no
+warmup, `cpu_baseline` (the CPU oracle on a bounded sample), `golden` (the reference's golden scenes), the short C5 leg
+of a multi-rank run, and the single-GPU proxy of the row split (`--emulate-ranks N`, default 8 on a one-rank run): every
+rank's share is rendered on this GPU in turn with the same step; the predicted N-GPU step time is the slowest share's,
+and `emulated_split.efficiency` = full-image time / (N x slowest share). `--no-cpu-baseline`,
+`--no-golden`, `--emulate-ranks 0` and `--c5-leg 0` switch single parts of `--full` off.
 """
 from __future__ import annotations
 
@@ -67,6 +74,34 @@ def golden_check():
     return {"scenes": len(per), "harness_pass": sum(v["harness_pct"] <= 2.0 for v in per.values()),
             "max_abs_delta_non_glass": max(non_glass),
             "max_abs_delta_all": max(v["max_abs_delta"] for v in per.values()), "per_scene": per}
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: the files' arrays, all together
+DUMP_SEED = 20240607  # (the row sample of an image above the limit)
+
+
+def dump_outputs(dirname: str, full, rays: int) -> dict:
+    """What a caller of the timed path receives from its last step, as DIR/<name>.npy: `image` (the gathered H x W x 3
+    float32 accumulation image of rank 0) and `rays` (float64, the step's closest-hit queries over all ranks). An image
+    above DUMP_LIMIT_BYTES (C5: 99.5 MB) is cut to a fixed, seeded sample of whole rows, in ascending order, and
+    `image_rows` (float64) names them."""
+    import numpy as np
+
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    img = full.detach().cpu().numpy().astype(np.float32, copy=False)
+    files = {"rays": np.array([float(rays)], dtype=np.float64)}
+    row_bytes = img[0].nbytes
+    budget = DUMP_LIMIT_BYTES - files["rays"].nbytes
+    if img.nbytes > budget:
+        keep = int(budget // (row_bytes + 8))  # (a row and its float64 entry in the row list)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(img.shape[0], size=keep, replace=False))
+        files["image_rows"] = rows.astype(np.float64)
+        img = img[rows]
+    files["image"] = np.ascontiguousarray(img)
+    for name, a in files.items():
+        np.save(out / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in files.items()}
 
 
 def log(msg: str) -> None:
@@ -366,10 +401,12 @@ def emulate_split(sd, knobs: dict, n: int, args, full_img, full_s: float, full_r
     }
 
 
-def run_leg(sd, knobs: dict, args, dist, rank: int, world: int, dev, steps: int, warmup: int, tag: str = "") -> dict:
+def run_leg(sd, knobs: dict, args, dist, rank: int, world: int, dev, steps: int, warmup: int, tag: str = "",
+            count_after: bool = False) -> dict:
     """One timed leg of the bench on this rank: the renderer for this rank's rows (8-row blocks dealt round-robin),
     `warmup` counting steps, then `steps` timed steps bracketed by a barrier + synchronize on both sides. A step =
-    reset, draw every frame (TIME0 + f * DTIME), copy the image into the rank's band, gather the bands on rank 0."""
+    reset, draw every frame (TIME0 + f * DTIME), copy the image into the rank's band, gather the bands on rank 0.
+    count_after (--full): without a warmup step, one counting draw after the timed region supplies the test counts."""
     import torch
 
     import scenes
@@ -442,14 +479,17 @@ def run_leg(sd, knobs: dict, args, dist, rank: int, world: int, dev, steps: int,
     barrier()
     L["elapsed"] = time.perf_counter() - t0
     if steps and uncounted:  # the timed kernels did not count: the per-step counts of a counting draw
-        if counted is None:  # (no warmup: one more draw after the timed region, rank-local, no collective)
+        if counted is None and count_after:  # (no warmup: one more draw after the timed region, rank-local, no collective)
             r.set_params(count_tests=1)
             r.reset_frame_count()
             r.draw_frames(sd.frames, TIME0, DTIME)
             st_c = r.stats()
             r.set_params(count_tests=0)
             counted = (st_c.box_tests, st_c.sphere_tests)
-        L["box_tests"], L["sphere_tests"] = counted[0] * steps, counted[1] * steps
+        if counted is not None:
+            L["box_tests"], L["sphere_tests"] = counted[0] * steps, counted[1] * steps
+    # (a plain run without a warmup step has no test counts: its line leaves the roofline block out)
+    L["tests_counted"] = not (steps and uncounted and counted is None)
     # this rank's report: rows, times, rays, its band's position-dependent checksum, and the GPU it drew on — the
     # renderer's (rt_get_device) next to torch's current device
     ordinal, pci = r.device()
@@ -504,9 +544,15 @@ def main() -> int:
                     help="sphere-scan kernel: 0 auto, 1 simple, 2 packed, 3 deferred, 4 culling BVH")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also: CPU baseline, golden-image check, the emulated 8-rank split (one "
+                         "rank) or the C5 leg (several ranks), the roofline's counting draw when there was no warmup; "
+                         "a plain run only times its steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's image and ray count as DIR/<name>.npy (rank 0)")
     ap.add_argument("--verify", action="store_true", help="rank 0 re-renders the image alone and compares")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-golden", action="store_true", help="skip the golden-image check (rank 0, after timing)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-golden", action="store_true", help="--full without the golden-image check (rank 0, after timing)")
     ap.add_argument("--cpu-rows", type=int, default=108)
     ap.add_argument("--cpu-frames", type=int, default=128)
     ap.add_argument("--row-block", type=int, default=None,
@@ -514,10 +560,10 @@ def main() -> int:
                          "interleaved rows); default ROW_BLOCK's per-workload choice")
     ap.add_argument("--emulate-ranks", type=int, default=None,
                     help="single-GPU proxy of the N-rank split: render every rank's share here in turn after the "
-                         "timed region (default 8 on a one-rank run, 0 = off)")
+                         "timed region (default with --full: 8 on a one-rank run; 0 = off)")
     ap.add_argument("--c5-leg", type=int, default=None,
-                    help="after the timed config, time a short C5 leg (BASELINE's 8-GPU config): default on for "
-                         "multi-rank runs, 1 forces it on one rank, 0 off")
+                    help="after the timed config, time a short C5 leg (BASELINE's 8-GPU config): default with --full on "
+                         "for multi-rank runs, 1 forces it on (one rank too), 0 off")
     ap.add_argument("--c5-steps", type=int, default=3)
     ap.add_argument("--c5-warmup", type=int, default=1)
     ap.add_argument("--launcher-selftest", action="store_true",
@@ -589,11 +635,11 @@ def main() -> int:
     # and sphere tests); the warmup draws count them (count_tests 1) for the per-ray figures of the line, the same
     # every step (bit-identical draws)
     knobs = timed_knobs(args.frames_per_launch, args.variant, args.schedule, args.tri_bvh, **extra)
-    L = run_leg(sd, knobs, args, dist, rank, world, dev, args.steps, args.warmup)
+    L = run_leg(sd, knobs, args, dist, rank, world, dev, args.steps, args.warmup, count_after=args.full)
     full, local_rows, elapsed, queries = L["full"], L["local_rows"], L["elapsed"], L["queries"]
     st_last, schedule, suspend, variant = L["st_last"], L["schedule"], L["suspend"], L["variant"]
     emulated = None
-    n_emul = args.emulate_ranks if args.emulate_ranks is not None else (8 if world == 1 else 0)
+    n_emul = args.emulate_ranks if args.emulate_ranks is not None else (8 if world == 1 and args.full else 0)
     if world == 1 and n_emul > 1:
         emulated = emulate_split(sd, knobs, n_emul, args, full, elapsed / args.steps, queries / args.steps)
 
@@ -617,7 +663,7 @@ def main() -> int:
     # BASELINE.json's 8-GPU config is C5 (4K x 4096 spp, row tiles + RCCL gather): after the headline leg a multi-rank
     # run times a short C5 leg too (1 warmup + 3 steps; ~1.2 s per step on 8 ranks), same partition, same report
     c5 = None
-    c5_on = args.c5_leg if args.c5_leg is not None else (world > 1 and args.config != "c5")
+    c5_on = args.c5_leg if args.c5_leg is not None else (args.full and world > 1 and args.config != "c5")
     if c5_on:
         # the headline leg's renderer (and its colour buffer) goes first: one leg's memory at a time
         del L["renderer"]
@@ -710,10 +756,12 @@ def main() -> int:
                 # render runs 1 learning + 2 ordered launches for C3, ~0.6 % slower)
                 "warm": bool(args.warmup > 0 and schedule == 2 and st_last.ordered_launches > 0),
             },
-            # The path is FP32-VALU issue bound (no MFMA: no dense contraction; HBM ~2 % busy). `achieved` =
-            # the FP32 FLOPs the kernel executes (its exact in-kernel test counters x FLOP per test, + the
-            # per-ray hit record / scatter) / the HIP-event time of its launches on the renderer's stream.
-            "roofline": {
+        }
+        # The path is FP32-VALU issue bound (no MFMA: no dense contraction; HBM ~2 % busy). `achieved` =
+        # the FP32 FLOPs the kernel executes (its exact in-kernel test counters x FLOP per test, + the
+        # per-ray hit record / scatter) / the HIP-event time of its launches on the renderer's stream.
+        if L["tests_counted"]:
+            out["roofline"] = {
                 "bound": "fp32-valu",
                 "achieved": round(executed_tflops, 3),
                 "peak": FP32_PEAK_TFLOPS,
@@ -745,8 +793,9 @@ def main() -> int:
                 "hbm_gbs_traffic": (round(traffic / (avg_launch_ms * 1e-3) / 1e9, 3) if traffic else None),
                 "hbm_frac": (round(traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if traffic else None),
                 "pmc": pmc_view(pmc),
-            },
-        }
+            }
+        if args.dump_outputs:
+            out["dumped"] = dump_outputs(args.dump_outputs, full, round(total_q / args.steps))
         # one GPU per rank under RCCL: no two ranks may share one (a gloo rehearsal on one GPU shares it by design)
         distinct = args.backend == "nccl"
         device_error = None
@@ -778,10 +827,10 @@ def main() -> int:
             out["c5"] = blk
         if emulated is not None:
             out["emulated_split"] = emulated
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("cpu baseline (oracle) ...")
             out["cpu_baseline"] = cpu_baseline(sd, cpu_threads(), args.cpu_rows, args.cpu_frames)
-        if not args.no_golden:
+        if args.full and not args.no_golden:
             out["golden"] = golden_check()
             log(f"golden: {out['golden']['harness_pass']}/{out['golden']['scenes']} pass the reference harness, "
                 f"max |delta| {out['golden']['max_abs_delta_non_glass']} (non-glass)")

@@ -13,6 +13,6 @@ for grp in \
   "SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INST_CYCLES_SMEM SQ_INST_LEVEL_SMEM SQ_LEVEL_WAVES SQ_CYCLES" \
   "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" ; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d "$out" -o "p$i" -- python3 bench.py --no-cpu-baseline "$@" > "$out/p$i.log" 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d "$out" -o "p$i" -- python3 bench.py --full --no-cpu-baseline "$@" > "$out/p$i.log" 2>&1
 done
 python3 scripts/pmc_summary.py "$out" ${PMC_KERNEL:-}

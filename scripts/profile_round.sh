@@ -9,7 +9,7 @@ tag="$1"; shift
 out="gpurun_out/$tag"
 mkdir -p "$out"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/prof" -o run --output-format csv -- \
-  python3 bench.py --no-cpu-baseline --no-golden "$@" > "$out/prof_bench.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline --no-golden "$@" > "$out/prof_bench.log" 2>&1
 find "$out/prof" -name "*kernel_stats.csv" -exec cp {} "$out/kernel_stats.csv" \;
 # (warmup 1: the timed launch deals in the learnt cost order, as the bench's; pmc_summary keeps the timed dispatches)
 scripts/pmc.sh "$out/pmc" --no-golden --steps 1 --warmup 1 --emulate-ranks 0 "$@" > "$out/pmc.log" 2>&1

@@ -31,6 +31,7 @@ uint32_t hrt_order_scratch_words(uint32_t ntiles);
 const char* hrt_last_kernel();
 void hrt_reset_last_kernel();
 hipError_t hrt_check_exact_math(unsigned long long n, uint32_t seed, unsigned long long* out_dev, hipStream_t st);
+hipError_t hrt_check_uniform_guards(unsigned long long n_waves, uint32_t seed, unsigned long long* out_dev, hipStream_t st);
 
 namespace {
 
@@ -1404,6 +1405,23 @@ int rt_check_exact_math(uint64_t n, uint32_t seed, uint64_t mismatches[3]) {
     if (e == hipSuccess) e = hipMemcpy(mismatches, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, std::string("rt_check_exact_math: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_check_uniform_guards(uint64_t n_waves, uint32_t seed, uint64_t out[RT_UGUARD_HELPERS * RT_UGUARD_WORDS]) {
+    if (!out) return fail(RT_ERR_ARG, "rt_check_uniform_guards: null");
+    if (n_waves == 0) return fail(RT_ERR_ARG, "rt_check_uniform_guards: no waves");
+    int dev = 0;
+    int rc = check_device(&dev);
+    if (rc) return rc;
+    constexpr size_t bytes = RT_UGUARD_HELPERS * RT_UGUARD_WORDS * sizeof(unsigned long long);
+    unsigned long long* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, bytes));
+    hipError_t e = hipMemset(d, 0, bytes);
+    if (e == hipSuccess) e = hrt_check_uniform_guards(n_waves, seed, d, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, std::string("rt_check_uniform_guards: ") + hipGetErrorString(e));
     return RT_OK;
 }
 

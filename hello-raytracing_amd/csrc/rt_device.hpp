@@ -305,12 +305,15 @@ __device__ __forceinline__ float div_exact(float x, float l) {
 
 // normalize() of any vector: the sequences above when every component's magnitude lies in [2^-40, 2^40] (then
 // dot is in [2^-80, 3 x 2^80] and the length and quotients inside their ranges), else the IEEE operations;
-// bit-identical to normalize() either way (GPU self-check: rt_check_exact_math).
+// bit-identical to normalize() either way (GPU self-check: rt_check_exact_math). minNum / maxNum drop a NaN
+// component, so the dot (NaN with any NaN component) joins the range test: the fast sequence's NaN would carry the
+// opposite sign bit of normalize()'s (rt_check_uniform_guards found it).
 __device__ __forceinline__ f3 normalize_exact(f3 a) {
     const float lo = fmin_ieee(fmin_ieee(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
     const float hi = fmax_ieee(fmax_ieee(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
-    if (lo >= 0x1p-40f && hi <= 0x1p40f) {
-        const RcpRN d = rcp_rn_setup(sqrt_rn_mid(dot(a, a)));
+    const float dd = dot(a, a);
+    if (lo >= 0x1p-40f && hi <= 0x1p40f && dd == dd) {
+        const RcpRN d = rcp_rn_setup(sqrt_rn_mid(dd));
         return mk(div_rn_mid(a.x, d), div_rn_mid(a.y, d), div_rn_mid(a.z, d));
     }
     return normalize(a);
@@ -331,9 +334,10 @@ __device__ __forceinline__ float sqrt_exact_u(float x) {
 __device__ __forceinline__ f3 normalize_exact_u(f3 a) {
     const float lo = fmin_ieee(fmin_ieee(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
     const float hi = fmax_ieee(fmax_ieee(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
-    const RcpRN d = rcp_rn_setup(sqrt_rn_mid(dot(a, a)));
+    const float dd = dot(a, a);
+    const RcpRN d = rcp_rn_setup(sqrt_rn_mid(dd));
     f3 q = mk(div_rn_mid(a.x, d), div_rn_mid(a.y, d), div_rn_mid(a.z, d));
-    const bool slow = !(lo >= 0x1p-40f && hi <= 0x1p40f);
+    const bool slow = !(lo >= 0x1p-40f && hi <= 0x1p40f && dd == dd);  // (dd == dd: no NaN component, as normalize_exact)
     if (__builtin_expect(__ballot(slow) != 0ull, 0)) {
         if (slow) q = normalize(a);
     }

@@ -3633,6 +3633,303 @@ hipError_t hrt_check_exact_math(unsigned long long n, uint32_t seed, unsigned lo
     return hipGetLastError();
 }
 
+// ---- self-check of the wave-uniform range guards (k_check_uniform_guards, below)
+namespace {
+
+constexpr uint32_t UG_HELPERS = 6, UG_WORDS = 10;
+
+// A copy of an operand the compiler cannot relate to the original: the helper under test computes from its own
+// registers, not from values shared with the reference computed beside it.
+__device__ __forceinline__ float ug_opaque(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ f3 ug_opaque(f3 a) { return mk(ug_opaque(a.x), ug_opaque(a.y), ug_opaque(a.z)); }
+__device__ __forceinline__ bool ug_same(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool ug_same(f3 a, f3 b) { return ug_same(a.x, b.x) && ug_same(a.y, b.y) && ug_same(a.z, b.z); }
+__device__ __forceinline__ float ug_bits(uint32_t sign, uint32_t biased, uint32_t m) {
+    return __uint_as_float((sign << 31) | (biased << 23) | (m & 0x7FFFFFu));
+}
+__device__ __forceinline__ float ug_pow2(int e) { return ug_bits(0u, (uint32_t)(127 + e), 0u); }
+// log-uniform magnitude in [2^lo, 2^hi) with a random significand, a random sign when `sgn`
+__device__ __forceinline__ float ug_mag(uint32_t& s, int lo, int hi, bool sgn) {
+    s = pcg_next(s);
+    const uint32_t e = (uint32_t)(127 + lo) + s % (uint32_t)(hi - lo);
+    const uint32_t m = pcg_next(s ^ 0x9E3779B9u);
+    return ug_bits(sgn ? (m >> 31) : 0u, e, m);
+}
+__device__ __forceinline__ float ug_nan(uint32_t h) { return __uint_as_float(0x7FC00000u | (h & 0x803FFFFFu)); }
+__device__ __forceinline__ bool ug_in(float x, float lo, float hi) { return x >= lo && x <= hi; }  // a NaN is outside
+// component k of v = x (selects: a reference to a component picked at run time would put v in memory)
+__device__ __forceinline__ void ug_set(f3& v, uint32_t k, float x) {
+    v.x = k == 0u ? x : v.x;
+    v.y = k == 1u ? x : v.y;
+    v.z = k >= 2u ? x : v.z;
+}
+
+// A ray aimed near a sphere of radius 0.5 gs three direction lengths away (|d.x| in [0.5, 1] ds, the origin outside the
+// sphere; about half of the rays miss): gs scales the geometry and ds the direction, both powers of two, so every
+// operand of the root scales exactly. At gs = ds = 1: a2 in [0.5, 6], a hit's numerator above 0.01.
+__device__ __forceinline__ void ug_ray(uint32_t& s, float gs, float ds, Ray& r, float4& g) {
+    const float sx = (pcg_next(s ^ 0x5bd1e995u) & 1u) ? -1.0f : 1.0f;
+    const f3 d = mk(sx * (0.5f + 0.5f * rng_float(s)), 2.0f * rng_float(s) - 1.0f, 2.0f * rng_float(s) - 1.0f);
+    const f3 o = mk(8.0f * rng_float(s) - 4.0f, 8.0f * rng_float(s) - 4.0f, 8.0f * rng_float(s) - 4.0f);
+    const f3 e = mk(0.8f * rng_float(s) - 0.4f, 0.8f * rng_float(s) - 0.4f, 0.8f * rng_float(s) - 0.4f);
+    const f3 c = o + 3.0f * d + e;
+    r.o = gs * o;
+    r.d = ds * d;
+    const float rad = 0.5f * gs;
+    g = float4{gs * c.x, gs * c.y, gs * c.z, rad * rad};
+}
+
+// One call's counts: lane h UG_WORDS + c of the wave accumulates column c of helper h (one atomic per wave at the end).
+// cmp: the lane's result is compared; oor: its operands lie outside the helper's documented fast range.
+template <uint32_t H>
+__device__ __forceinline__ void ug_tally(unsigned long long& acc, bool cmp, bool bad, bool oor, bool fast_differs,
+                                         bool partial, bool unneeded_oor) {
+    const uint32_t nc = (uint32_t)__popcll(__ballot(cmp)), no = (uint32_t)__popcll(__ballot(cmp && oor));
+    const uint32_t vals[UG_WORDS] = {
+        (uint32_t)__popcll(__ballot(cmp && bad)), nc, no, (uint32_t)__popcll(__ballot(cmp && oor && fast_differs)),
+        no == 0u ? 1u : 0u,                        // no compared lane takes the fallback
+        no == 1u && nc > 1u ? 1u : 0u,             // exactly one of several
+        no > 1u && no < nc ? 1u : 0u,              // some, not all
+        no != 0u && no == nc ? 1u : 0u,            // every one
+        partial ? 1u : 0u, (uint32_t)__popcll(__ballot(unneeded_oor))};
+    const uint32_t lane = __lane_id();
+#pragma unroll
+    for (uint32_t c = 0; c < UG_WORDS; c++)
+        if (lane == H * UG_WORDS + c) acc += vals[c];
+}
+
+}  // namespace
+
+// Self-check of the range guards written as wave-uniform branches (sqrt_exact_u, normalize_exact_u: rt_device.hpp;
+// candidate_t, div_by_radius3_u, div_by_len_rng_u, div_cam_u: above): the fast sequence runs for every lane and a
+// __ballot decides whether the wave recomputes its out-of-range lanes. One unit of work is one 64-lane wave calling each
+// of the six helpers once — the very inline functions the product kernels call. Every lane holds two operand sets per
+// helper, one inside the helper's fast range (its edges included) and one outside it (classes: include/hrt.h), both
+// hashed from (wave, lane, seed); the wave's pattern (wave index mod 8) decides which lanes get the outside set and
+// which lanes are active at the call, at hashed lane positions:
+//   0-5  every lane active; 0, 1, 31, 32, 63, 64 lanes outside
+//   6    the calls sit in a divergent branch with 1..63 lanes active, a hashed subset of them outside
+//   7    as 6, the active lanes all inside
+// (the inactive lanes of 6 and 7 hold outside operands, which must not reach an active lane's result). The references
+// (the IEEE operations, table in include/hrt.h) are computed outside the divergent region and compared bit for bit, NaNs
+// included. out[helper x 10 + column], columns in include/hrt.h; "outside the fast range" (columns 2-7, 9) is this
+// kernel's own statement of each documented range, and column 3 counts the outside lanes on which the fast sequence
+// alone (no fallback, written out here) differs from the IEEE result: the lanes a broken fallback would show on.
+__global__ __launch_bounds__(256) void k_check_uniform_guards(unsigned long long n_waves, uint32_t seed,
+                                                              unsigned long long* out) {
+    const uint32_t lane = __lane_id();
+    unsigned long long acc = 0;  // lane k: counter word k
+    const unsigned long long stride = (unsigned long long)gridDim.x * 4u;
+    for (unsigned long long w = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6); w < n_waves; w += stride) {
+        const uint32_t hw = pcg_next((uint32_t)w * 2654435761u ^ seed ^ (uint32_t)(w >> 32) * 40503u);  // wave-uniform
+        const uint32_t hw2 = pcg_next(hw), hw3 = pcg_next(hw2);
+        const uint32_t pat = (uint32_t)w & 7u;
+        const bool partial = pat >= 6u;
+        // two hashed lane orders (odd multiplier, offset, xor: bijections of 0..63): the outside lanes and the active lanes
+        const uint32_t rank = (((lane * ((hw >> 8) | 1u)) + hw) ^ (hw >> 16)) & 63u;
+        const uint32_t rank_a = (((lane * ((hw2 >> 8) | 1u)) + hw2) ^ (hw2 >> 16)) & 63u;
+        const uint32_t nslow = pat == 0u ? 0u : pat == 1u ? 1u : pat == 2u ? 31u : pat == 3u ? 32u : pat == 4u ? 63u : 64u;
+        const bool active = !partial || rank_a < 1u + hw3 % 63u;
+        const uint32_t dens = (hw3 >> 8) % 9u;  // pattern 6: eighths of the active lanes outside (0: none, 8: all)
+        const uint32_t sl = pcg_next(hw ^ (lane * 0x9E3779B9u + 0x85EBCA6Bu));  // the lane's stream
+        // helper h's outside lanes
+        auto outside = [&](uint32_t h) {
+            if (!partial) return ((rank * (2u * h + 1u) + 11u * h) & 63u) < nslow;
+            if (!active) return true;
+            return pat == 6u && (pcg_next(sl ^ (h * 0x632BE5ABu)) >> 13 & 7u) < dens;
+        };
+
+        {   // 0: sqrt_exact_u vs __builtin_sqrtf
+            uint32_t s = pcg_next(sl + 0x1000u);
+            float xin = ug_mag(s, -100, 100, false);
+            s = pcg_next(s);
+            if ((s & 31u) == 0u) xin = 0x1p-100f;
+            if ((s & 31u) == 1u) xin = 0x1p100f;
+            s = pcg_next(s);
+            const uint32_t cls = s % 7u, m = pcg_next(s);
+            const float xout = cls == 0u ? 0.0f
+                             : cls == 1u ? __uint_as_float(1u + m % 0x7FFFFFu)                 // a denormal
+                             : cls == 2u ? __uint_as_float(__float_as_uint(0x1p-100f) - 1u)
+                             : cls == 3u ? __uint_as_float(__float_as_uint(0x1p100f) + 1u)
+                             : cls == 4u ? __builtin_inff()
+                             : cls == 5u ? -ug_mag(s, -100, 100, false)
+                                         : ug_nan(m);
+            const float x = outside(0u) ? xout : xin;
+            const float ref = __builtin_sqrtf(x), fast = sqrt_rn_mid(x);
+            const bool oor = !ug_in(x, 0x1p-100f, 0x1p100f);
+            float res = 0.0f;
+            if (active) res = sqrt_exact_u(ug_opaque(x));
+            ug_tally<0>(acc, active, !ug_same(res, ref), oor, !ug_same(fast, ref), partial, false);
+        }
+        {   // 1: normalize_exact_u vs normalize
+            uint32_t s = pcg_next(sl + 0x2000u);
+            f3 vin = mk(ug_mag(s, -40, 40, true), ug_mag(s, -40, 40, true), ug_mag(s, -40, 40, true));
+            s = pcg_next(s);
+            if ((s & 15u) == 0u) ug_set(vin, (s >> 4) % 3u, ug_bits(s >> 31, 127u - 40u, 0u));
+            if ((s & 15u) == 1u) ug_set(vin, (s >> 4) % 3u, ug_bits(s >> 31, 127u + 40u, 0u));
+            f3 vout = mk(ug_mag(s, -40, 40, true), ug_mag(s, -40, 40, true), ug_mag(s, -40, 40, true));
+            s = pcg_next(s);
+            const uint32_t cls = s % 6u, k = (s >> 8) % 3u, sg = s >> 31, m = pcg_next(s);
+            if (cls == 0u) ug_set(vout, k, ug_bits(sg, 0u, 0u));
+            if (cls == 1u) ug_set(vout, k, __uint_as_float((__float_as_uint(0x1p-40f) - 1u) | (sg << 31)));
+            if (cls == 2u) ug_set(vout, k, __uint_as_float((__float_as_uint(0x1p40f) + 1u) | (sg << 31)));
+            if (cls == 3u) vout = mk(ug_mag(s, -81, -78, true), ug_mag(s, -81, -78, true), ug_mag(s, -81, -78, true));
+            if (cls == 4u) vout = mk(ug_mag(s, 59, 62, true), ug_mag(s, 59, 62, true), ug_mag(s, 59, 62, true));
+            if (cls == 5u) ug_set(vout, k, ug_nan(m));
+            const f3 v = outside(1u) ? vout : vin;
+            const f3 ref = normalize(v);
+            const RcpRN d = rcp_rn_setup(sqrt_rn_mid(dot(v, v)));
+            const f3 fast = mk(div_rn_mid(v.x, d), div_rn_mid(v.y, d), div_rn_mid(v.z, d));
+            const bool oor = !(ug_in(__builtin_fabsf(v.x), 0x1p-40f, 0x1p40f) && ug_in(__builtin_fabsf(v.y), 0x1p-40f, 0x1p40f) &&
+                               ug_in(__builtin_fabsf(v.z), 0x1p-40f, 0x1p40f));
+            f3 res = mk(0.0f, 0.0f, 0.0f);
+            if (active) res = normalize_exact_u(ug_opaque(v));
+            ug_tally<1>(acc, active, !ug_same(res, ref), oor, !ug_same(fast, ref), partial, false);
+        }
+        {   // 2: candidate_t vs exact_t_geo<false>, on the lanes sphere_candidate accepts (the others: need = false)
+            uint32_t s = pcg_next(sl + 0x3000u);
+            Ray rin, rout;
+            float4 gin, gout;
+            s = pcg_next(s);
+            ug_ray(s, ug_pow2((int)(s % 17u) - 8), ug_pow2((int)((s >> 8) % 17u) - 8), rin, gin);
+            s = pcg_next(s);
+            const uint32_t cls = s & 7u;
+            //            disc small  disc large  a2 small  a2 large  a2 denormal  |num| small  |num| large
+            const int gs = cls == 1u ? -28 : cls == 2u ? 52 : cls == 6u ? -45 : cls == 7u ? 45 : 0;
+            const int ds = cls == 1u ? -28 : cls == 3u ? -50 : cls == 4u ? 40 : cls == 5u ? -65 : cls == 6u ? -22 : cls == 7u ? 22 : 0;
+            ug_ray(s, ug_pow2(gs), ug_pow2(ds), rout, gout);
+            if (cls == 0u) {
+                // the origin exactly on the sphere: centre and offset small integers, |offset| = radius an integer, so
+                // c == 0, disc = RN(b b), its root |b| and the numerator 0, all exactly
+                s = pcg_next(s);
+                const uint32_t t = s % 3u, rot = (s >> 4) % 3u;
+                const float p = t == 0u ? 3.0f : t == 1u ? 1.0f : 2.0f, q = t == 0u ? 4.0f : t == 1u ? 2.0f : 3.0f,
+                            u = t == 0u ? 0.0f : t == 1u ? 2.0f : 6.0f, rad = t == 0u ? 5.0f : t == 1u ? 3.0f : 7.0f;
+                f3 v = rot == 0u ? mk(p, q, u) : rot == 1u ? mk(u, p, q) : mk(q, u, p);
+                if (s & 0x100u) v.x = -v.x;
+                if (s & 0x200u) v.y = -v.y;
+                if (s & 0x400u) v.z = -v.z;
+                const f3 c = mk((float)((s >> 12) % 17u) - 8.0f, (float)((s >> 17) % 17u) - 8.0f, (float)((s >> 22) % 17u) - 8.0f);
+                rout.o = c + v;
+                rout.d = mk(0.5f * rng_float(s) - 0.25f, 0.5f * rng_float(s) - 0.25f, 0.5f * rng_float(s) - 0.25f) - v;
+                gout = float4{c.x, c.y, c.z, rad * rad};
+            }
+            const bool outs = outside(2u);
+            const Ray r = outs ? rout : rin;
+            const float4 g = outs ? gout : gin;
+            const float a = dot(r.d, r.d), a4 = 4.0f * a, a2 = 2.0f * a;
+            const bool cand = sphere_candidate(g, r, a4);
+            const float ref = exact_t_geo<false>(g, r, a4, a2);
+            // the root's operands, restated
+            const float ocx = r.o.x - g.x, ocy = r.o.y - g.y, ocz = r.o.z - g.z;
+            const float bd = __builtin_fmaf(ocz, r.d.z, __builtin_fmaf(ocy, r.d.y, ocx * r.d.x)), b = bd + bd;
+            const float c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx)) - g.w;
+            const float disc = __builtin_fmaf(b, b, (-a4) * c);
+            const bool oor = !(ug_in(disc, 0x1p-100f, 0x1p100f) && ug_in(__builtin_fabsf(-b - __builtin_sqrtf(disc)), 0x1p-60f, 0x1p60f) &&
+                               ug_in(a2, 0x1p-60f, 0x1p60f));
+            const float fast = div_rn_mid(-b - sqrt_rn_mid(disc), rcp_rn_setup(a2));
+            float res = 0.0f;
+            if (active) {
+                const Ray rc{ug_opaque(r.o), ug_opaque(r.d)};
+                res = candidate_t(float4{ug_opaque(g.x), ug_opaque(g.y), ug_opaque(g.z), ug_opaque(g.w)}, rc, ug_opaque(a4),
+                                  ug_opaque(a2), cand);
+            }
+            ug_tally<2>(acc, active && cand, !ug_same(res, ref), oor, !ug_same(fast, ref), partial, active && !cand && oor);
+        }
+        {   // 3: div_by_radius3_u vs x / radius per component
+            uint32_t s = pcg_next(sl + 0x4000u);
+            float rad_in = ug_mag(s, -60, 60, false);
+            f3 nin = mk(ug_mag(s, -60, 60, true), ug_mag(s, -60, 60, true), ug_mag(s, -60, 60, true));
+            s = pcg_next(s);
+            if ((s & 15u) == 0u) rad_in = (s & 16u) ? 0x1p-60f : 0x1p60f;
+            if ((s & 0xF00u) == 0u) ug_set(nin, (s >> 12) % 3u, ug_bits(s >> 31, (s & 0x8000u) ? 127u - 60u : 127u + 60u, 0u));
+            float rad_out = ug_mag(s, -60, 60, false);
+            f3 nout = mk(ug_mag(s, -60, 60, true), ug_mag(s, -60, 60, true), ug_mag(s, -60, 60, true));
+            s = pcg_next(s);
+            const uint32_t cls = s & 3u, k = (s >> 8) % 3u;
+            if (cls == 0u) rad_out = (s & 0x10u) ? ug_mag(s, -90, -61, false) : ug_mag(s, 61, 90, false);
+            if (cls == 1u) ug_set(nout, k, ug_bits(s >> 31, 0u, 0u));
+            if (cls == 2u) ug_set(nout, k, ug_mag(s, -90, -60, true));
+            if (cls == 3u) ug_set(nout, k, ug_mag(s, 61, 90, true));
+            const bool outs = outside(3u);
+            const f3 n = outs ? nout : nin;
+            const float rad = outs ? rad_out : rad_in;
+            const float inv = ug_in(rad, 0x1p-60f, 0x1p60f) ? 1.0f / rad : 0.0f;  // SphereAux::inv_radius
+            const f3 ref = mk(n.x / rad, n.y / rad, n.z / rad);
+            const RcpRN d{rad, inv};
+            const f3 fast = mk(div_rn_mid(n.x, d), div_rn_mid(n.y, d), div_rn_mid(n.z, d));
+            const bool oor = !(inv != 0.0f && ug_in(__builtin_fabsf(n.x), 0x1p-60f, 0x1p60f) &&
+                               ug_in(__builtin_fabsf(n.y), 0x1p-60f, 0x1p60f) && ug_in(__builtin_fabsf(n.z), 0x1p-60f, 0x1p60f));
+            f3 res = mk(0.0f, 0.0f, 0.0f);
+            if (active) res = div_by_radius3_u(ug_opaque(n), ug_opaque(rad), ug_opaque(inv));
+            ug_tally<3>(acc, active, !ug_same(res, ref), oor, !ug_same(fast, ref), partial, false);
+        }
+        {   // 4: div_by_len_rng_u vs div_by_len_rng<false>
+            uint32_t s = pcg_next(sl + 0x5000u);
+            float ain = rng_float(s), bin = rng_float(s);
+            s = pcg_next(s);
+            if ((s & 7u) == 0u) ain = 0.0f;
+            if ((s & 7u) == 1u) bin = 0.0f;
+            if ((s & 7u) == 2u) ain = (float)(1u + (s >> 8) % 16u) * 0x1p-32f;
+            if ((s & 7u) == 3u) bin = (float)(1u + (s >> 8) % 16u) * 0x1p-32f;
+            if (ain == 0.0f && bin == 0.0f) bin = 1.0f;
+            s = pcg_next(s);
+            const uint32_t cls = s % 3u, m = pcg_next(s);
+            float aout = rng_float(s), bout = rng_float(s);
+            if (cls == 0u) aout = bout = 0.0f;
+            if (cls == 1u) { aout = ug_mag(s, -61, -58, false); bout = ug_mag(s, -61, -58, false); }
+            if (cls == 2u) { if (m & 0x100u) aout = ug_nan(m); else bout = ug_nan(m); }
+            const bool outs = outside(4u);
+            const float a = outs ? aout : ain, b = outs ? bout : bin;
+            float ra, rb;
+            div_by_len_rng<false>(a, b, ra, rb);
+            const float d = __builtin_fmaf(b, b, a * a);
+            const RcpRN rr = rcp_rn_setup(sqrt_rn_mid(d));
+            const float fa = div_rn_mid(a, rr), fb = div_rn_mid(b, rr);
+            const bool oor = !(d >= 0x1p-100f);
+            float qa = 0.0f, qb = 0.0f;
+            if (active) div_by_len_rng_u(ug_opaque(a), ug_opaque(b), qa, qb);
+            ug_tally<4>(acc, active, !(ug_same(qa, ra) && ug_same(qb, rb)), oor, !(ug_same(fa, ra) && ug_same(fb, rb)), partial, false);
+        }
+        {   // 5: div_cam_u vs x / l
+            uint32_t s = pcg_next(sl + 0x6000u);
+            s = pcg_next(s);
+            const bool pixels = (s & 1u) != 0u;  // l = image extent - 1, x = pixel + 0.5 + jitter; else log-uniform operands
+            float lin = pixels ? (float)(1u + (s >> 8) % 16383u) : ug_mag(s, -60, 60, false);
+            float xin = pixels ? rng_float(s) * (lin + 1.0f) + 0.5f : ug_mag(s, -60, 60, false);
+            s = pcg_next(s);
+            if ((s & 15u) == 0u) xin = (s & 16u) ? 0x1p-60f : 0x1p60f;
+            if ((s & 0xF00u) == 0u) lin = (s & 0x1000u) ? 0x1p-60f : 0x1p60f;
+            float lout = (s & 0x2000u) ? (float)(1u + (s >> 16) % 16383u) : ug_mag(s, -60, 60, false);
+            float xout = ug_mag(s, -60, 60, false);
+            s = pcg_next(s);
+            const uint32_t cls = s % 5u, m = pcg_next(s);
+            if (cls == 0u) lout = (m & 3u) == 0u ? 0.0f : (m & 4u) ? ug_mag(s, -90, -61, false) : ug_mag(s, 61, 90, false);
+            if (cls == 1u) xout = 0.0f;
+            if (cls == 2u) xout = ug_mag(s, -90, -60, false);
+            if (cls == 3u) xout = ug_mag(s, 61, 90, false);
+            if (cls == 4u) xout = ug_nan(m);
+            const bool outs = outside(5u);
+            const float x = outs ? xout : xin, l = outs ? lout : lin;
+            const float inv = ug_in(l, 0x1p-60f, 0x1p60f) ? 1.0f / l : 0.0f;  // CamDev::inv_wm1 / inv_hm1
+            const float ref = x / l, fast = div_rn_mid(x, RcpRN{l, inv});
+            const bool oor = !(inv != 0.0f && ug_in(x, 0x1p-60f, 0x1p60f));
+            float res = 0.0f;
+            if (active) res = div_cam_u(ug_opaque(x), ug_opaque(l), ug_opaque(inv));
+            ug_tally<5>(acc, active, !ug_same(res, ref), oor, !ug_same(fast, ref), partial, false);
+        }
+    }
+    if (lane < UG_HELPERS * UG_WORDS && acc) atomicAdd(out + lane, acc);
+}
+
+hipError_t hrt_check_uniform_guards(unsigned long long n_waves, uint32_t seed, unsigned long long* out_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_check_uniform_guards, dim3(4096), dim3(256), 0, st, n_waves, seed, out_dev);
+    return hipGetLastError();
+}
+
 // Demangled-symbol form of the kernel a draw ran ("k_trace_split<true>"): rt_stats.kernel, and the key
 // bench.py matches against rocprofv3 summaries.
 // Per host thread (renderers driven from several threads each see their own launch); renderer.cpp copies it

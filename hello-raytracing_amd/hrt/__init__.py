@@ -3,7 +3,8 @@
 The compute path is lib/libhrt.so (HIP kernels for gfx950 behind the C-ABI of include/hrt.h); this
 package is the host-side mirror of the reference's Rust scene API plus ctypes plumbing.
 """
-from ._lib import (LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
+from . import _lib
+from ._lib import (UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
                    lib)
 from .scene import (CAMERA_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
@@ -16,10 +17,22 @@ def device_count() -> int:
     return int(lib().rt_device_count())
 
 
+def check_uniform_guards(n_waves: int, seed: int) -> dict:
+    """rt_check_uniform_guards (include/hrt.h): the GPU self-check of the wave-uniform range guards on n_waves waves,
+    as {helper: {column: count}} for the six helpers (UGUARD_HELPERS) by ten columns (UGUARD_COLUMNS). Raises RtError
+    without a gfx950 device or on bad arguments."""
+    import ctypes as C
+
+    out = (C.c_uint64 * (len(UGUARD_HELPERS) * len(UGUARD_COLUMNS)))()
+    _lib.check(lib().rt_check_uniform_guards(int(n_waves), int(seed) & 0xFFFFFFFF, out), "rt_check_uniform_guards")
+    w = len(UGUARD_COLUMNS)
+    return {h: {c: int(out[i * w + j]) for j, c in enumerate(UGUARD_COLUMNS)} for i, h in enumerate(UGUARD_HELPERS)}
+
+
 __all__ = [
     "LIB_PATH", "RT_FOLD_AUTO", "RT_FOLD_BUFFER", "RT_FOLD_NEXT", "RT_FOLD_RING", "RT_MODE_MIXED", "RT_SCHEDULE_AUTO", "RT_SCHEDULE_QUEUE", "RT_SCHEDULE_TILES", "RT_MODE_SPHERE", "RT_MODE_TRIS", "RtError", "RtParams", "RtStats", "lib",
     "CAMERA_DTYPE", "DIELECTRIC", "LAMBERTIAN", "MATERIAL_DTYPE", "MAX_OBJECT_IN_SCENE", "METAL", "NODE_DTYPE",
     "PI", "SPHERE_DTYPE", "TRIANGLE_DTYPE", "Camera", "ComparisonError", "Material", "Mesh", "OrbitCamera", "Renderer",
     "SceneSphere", "SceneTris", "Sphere", "Tree", "Vec3", "compare_ppm_images", "f32", "ppm_from_image",
-    "read_asset", "render_ppm", "spheres_array", "device_count",
+    "read_asset", "render_ppm", "spheres_array", "device_count", "check_uniform_guards", "UGUARD_COLUMNS", "UGUARD_HELPERS",
 ]

@@ -28,6 +28,12 @@ RT_MODE_TRIS = 1
 RT_MODE_MIXED = 2
 RT_SCHEDULE_AUTO, RT_SCHEDULE_TILES, RT_SCHEDULE_QUEUE = 0, 1, 2
 RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_RING, RT_FOLD_NEXT = 0, 1, 2, 3
+# rt_check_uniform_guards: out[helper * RT_UGUARD_WORDS + column] (include/hrt.h)
+UGUARD_HELPERS = ("sqrt_exact_u", "normalize_exact_u", "candidate_t", "div_by_radius3_u", "div_by_len_rng_u",
+                  "div_cam_u")
+UGUARD_COLUMNS = ("mismatches", "compared", "outside", "outside_fast_differs", "calls_none_outside",
+                  "calls_one_outside", "calls_some_outside", "calls_all_outside", "calls_partial_exec",
+                  "outside_unneeded")
 
 
 class RtParams(C.Structure):
@@ -110,6 +116,7 @@ SIGNATURES = {
     "rt_get_raw_counters": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "rt_diagnostic_build": (C.c_int, []),
     "rt_check_exact_math": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "rt_check_uniform_guards": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "rt_get_wave_trace": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_size_t]),
     "rt_get_device": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_last_error": (C.c_char_p, []),

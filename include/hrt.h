@@ -261,6 +261,39 @@ int rt_get_wave_trace(rt_renderer *r, uint64_t *out, size_t n_words);
  * All three must be 0. */
 int rt_check_exact_math(uint64_t n, uint32_t seed, uint64_t mismatches[3]);
 
+/* Self-check of the same sequences' range guards in their wave-uniform form (the fast sequence for every lane, one
+ * __ballot deciding whether the wave recomputes its out-of-range lanes with the IEEE operation): the six inline helpers
+ * the product kernels call, each called once per 64-lane wave on n_waves waves and compared bit for bit (NaNs too) with
+ *   0 sqrt_exact_u       __builtin_sqrtf            3 div_by_radius3_u   x / radius per component
+ *   1 normalize_exact_u  normalize                  4 div_by_len_rng_u   div_by_len_rng<false>
+ *   2 candidate_t        exact_t_geo<false>, on the lanes sphere_candidate accepts (the others are passed need = false)
+ *                                                   5 div_cam_u          x / l
+ * Every lane holds operands inside the helper's fast range (edges included) and operands outside it, hashed from
+ * (wave, lane, seed); the wave's pattern (wave index mod 8) picks the outside lanes at hashed positions: 0, 1, 31, 32, 63
+ * or all 64 of a full wave; or a call inside a divergent branch with 1..63 lanes active, a hashed subset of them outside
+ * (from none to all); or such a call whose only outside operands sit in the inactive lanes (the inactive lanes always
+ * hold outside operands). Outside classes, drawn uniformly per lane:
+ *   sqrt_exact_u      +0, a denormal, 2^-100 - 1 ulp, 2^100 + 1 ulp, +inf, a negative value, NaN
+ *   normalize_exact_u a zero component, one at 2^-40 - 1 ulp, one at 2^40 + 1 ulp, all near 2^-80 (the dot underflows
+ *                     to 0), all near 2^60, a NaN component; every sign
+ *   candidate_t       the origin exactly on the sphere (integer coordinates: c == 0 and a zero numerator), disc below
+ *                     2^-100, disc above 2^100 (r^2 = 2^102), 2a below 2^-60 (|d| near 2^-50), above 2^60 (|d| near
+ *                     2^40), denormal (|d| near 2^-65), the numerator below 2^-60 and above 2^60
+ *   div_by_radius3_u  inv_radius == 0 (radius outside [2^-60, 2^60]), a zero component, one below 2^-60, one above 2^60
+ *   div_by_len_rng_u  both operands 0, both near 2^-60, a NaN operand
+ *   div_cam_u         inv == 0 (l = 0 or outside [2^-60, 2^60]), x = 0, x below 2^-60, x above 2^60, NaN
+ * out[helper * RT_UGUARD_WORDS + column], columns (lanes unless "calls"; "outside" by the check's own statement of the
+ * documented range, not by reading the helper):
+ *   0 mismatches (must be 0)   1 lanes compared   2 compared lanes outside the fast range
+ *   3 of those, lanes where the fast sequence alone (no fallback) differs from the IEEE result: the lanes on which a
+ *     fallback that did not run would show
+ *   calls by their compared lanes outside the range: 4 none, 5 exactly one of several, 6 two or more but not all,
+ *   7 every one   8 calls under a partial exec mask   9 candidate_t: outside lanes passed need = false
+ * (diagnostics). */
+#define RT_UGUARD_HELPERS 6u
+#define RT_UGUARD_WORDS 10u
+int rt_check_uniform_guards(uint64_t n_waves, uint32_t seed, uint64_t out[RT_UGUARD_HELPERS * RT_UGUARD_WORDS]);
+
 /* The GPU a renderer draws on (no reference counterpart; the multi-GPU bench checks every rank's renderer against
  * its torch device): the HIP device ordinal that was current at rt_create, and that device's PCI location
  * {domain, bus, device}. A process must load ONE HIP runtime for the ordinal to mean what the caller's runtime
@@ -270,7 +303,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
 /* ABI guard (no reference counterpart): rt_params and rt_stats grow at their ends between versions, and rt_set_params
  * / rt_get_stats copy this header's sizes. A caller built against another header checks *version == RT_ABI_VERSION (or
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
-#define RT_ABI_VERSION 6u /* 6: rt_params.packet (round 6); 5: rt_params.cost_order, rt_stats.ordered_launches */
+#define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
+                             5: rt_params.cost_order, rt_stats.ordered_launches */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

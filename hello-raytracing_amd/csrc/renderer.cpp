@@ -141,6 +141,10 @@ uint32_t local_rows_of(uint32_t H, uint32_t row0, uint32_t step, uint32_t block)
     return (uint32_t)((nblocks - 1) * block + std::min<uint64_t>(block, H - last0));
 }
 
+// The descent hold of k_trace_split<LNODES> (rt_kernels.hip bvh_run<.., HOLD>): 0 = off. Not an rt_params field: a
+// product caller has no use for it; hrt_testing.h moves it for the tests and the sweeps.
+constexpr uint32_t DESCENT_HOLD_DEFAULT = 12u;
+
 }  // namespace
 
 struct rt_renderer {
@@ -210,6 +214,7 @@ struct rt_renderer {
     uint32_t last_schedule = 0;
     uint32_t last_suspend = 0;
     uint32_t test_ring_slots_max = 0, test_fail_alloc_above_mb = 0;  // hrt_testing.h fault injection
+    uint32_t descent_hold = DESCENT_HOLD_DEFAULT;  // k_trace_split<LNODES>'s descent hold (hrt_testing.h moves it)
     uint32_t ring_slots = 0;  // fold-ring slots of the last sample-queue draw
     uint32_t ring_tiles = 0, ring_nchunks = 0;  // (diagnostics: HRT_RING_DUMP)
     size_t ring_ctl_words = 0;
@@ -770,6 +775,8 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         r->last_fold_next = fold_next;
         // (suspend_below 0: the same kernels with a threshold no wave reaches, 1 walking lane: no suspension)
         P.suspend_below = split ? std::max(r->params.suspend_below, 1u) : 0u;
+        // (the sphere program's split kernel takes its descent hold in the same word, bits 8..15)
+        if (split && r->mode == RT_MODE_SPHERE) P.suspend_below |= r->descent_hold << 8;
         r->last_suspend = split ? r->params.suspend_below : 0u;
         P.job_frames = jf;
         HIP_TRY(hipEventRecord(r->ev_start, r->stream));
@@ -1242,6 +1249,13 @@ int rt_testing_set_faults(rt_renderer* r, uint32_t ring_slots_max, uint32_t fail
     if (!r) return fail(RT_ERR_ARG, "rt_testing_set_faults: null");
     r->test_ring_slots_max = ring_slots_max;
     r->test_fail_alloc_above_mb = fail_alloc_above_mb;
+    return RT_OK;
+}
+
+int rt_testing_set_descent_hold(rt_renderer* r, uint32_t hold) {
+    if (hold > 64) return fail(RT_ERR_ARG, "rt_testing_set_descent_hold: hold must be 0..64");
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_descent_hold: null");
+    r->descent_hold = hold;
     return RT_OK;
 }
 

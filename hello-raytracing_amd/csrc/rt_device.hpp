@@ -178,7 +178,8 @@ struct KParams {
     uint32_t tail_shift;
     uint32_t tiles_w, tiles_h;    // 8x8 tiles over W x nrows
     uint32_t job_frames, nchunks; // frames per job (a job = one tile x job_frames frames), chunks per tile
-    uint32_t suspend_below;       // k_trace_split: suspend the walks once fewer lanes than this still walk
+    uint32_t suspend_below;       // k_trace_split: suspend the walks once fewer lanes than this still walk (bits 0..7;
+                                  // the sphere program's k_trace_split: bits 8..15 the descent hold, bvh_run<.., HOLD>)
     uint32_t tri_small;           // k_trace_split_tris<.., SMALL>: 16-bit triangle lists + the heap top in LDS
     // frame-block work stealing (k_trace_split / k_trace_split_tris with the sample buffer; rt_kernels.hip steal_block)
     unsigned long long* steal_slots;  // one per wave: (job + 1) << 32 | frames claimed; zeroed per launch

@@ -430,16 +430,21 @@ __device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz
     return tmin <= tmax && tmin <= bt;
 }
 
+#ifndef HRT_BTEST
+#define HRT_BTEST 1
+#endif
 // NOOVF: the stack cannot overflow — a tree of depth <= STACK (renderer.cpp gates k_trace_split<LNODES> and the
 // mixed kernels' 8-entry stack on depth <= 8): visiting a node of depth d the stack holds at most d entries (one
 // pending sibling per level above it), so a push at an internal node (d <= depth - 1) leaves at most depth. The
 // push then needs no bound check and the walk no overflow flag (5 VALU of a ~50-VALU box step).
 // SO (with H16; Q from bvh_begin<.., SO>): box_hit_so.
 template <bool SUSPEND, int STACK = BVH_STACK, bool SELECT = false, bool H16 = false, uint32_t LS = 256,
-          bool NOOVF = false, bool SO = false, bool COUNT = true>
+          bool NOOVF = false, bool SO = false, bool COUNT = true, bool HOLD = false>
 __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery& Q, uint32_t* stack,
-                                        Tally& tally, uint32_t below, const uint4* __restrict__ hn = nullptr) {
+                                        Tally& tally, uint32_t below, const uint4* __restrict__ hn = nullptr,
+                                        uint32_t hold = 0u) {
     static_assert(!SO || H16, "the sign-ordered box test reads fp16 pairs");
+    static_assert(!HOLD || (NOOVF && SO && HRT_BTEST), "the descent hold lives in the bottom-tested descent loop");
     const float4* __restrict__ nodes = P.bvh_nodes;
     const Slab S = Q.S;
     // SO: the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds)
@@ -454,9 +459,6 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
     // overflow and finished are kept as integers (VGPRs): an i1 lane mask carried through the nested
     // divergent loops of k_trace_split was observed to keep stale overflow bits (sticky full scans)
     uint32_t overflow = 0u, finished = 0u;
-#ifndef HRT_BTEST
-#define HRT_BTEST 1
-#endif
 #ifndef HRT_LEAFIV
 #define HRT_LEAFIV 1
 #endif
@@ -477,6 +479,21 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
             tally.lwalk++;
             if (first_active_lane()) tally.wwalk++;
 #endif
+            // HOLD (k_trace_split; `hold` lanes, 0 = off): the descent loop below runs until its last lane has reached a
+            // leaf or missed, so its late trips run for a handful of lanes while the others wait. With the hold the
+            // whole wave leaves the loop after a step that fewer than `hold` lanes would follow with another one, if
+            // other walking lanes wait: a held lane keeps its internal node, skips the leaf block and the pop, and
+            // takes its next step in the next outer iteration beside the lanes that did pop. Every lane takes the
+            // same steps in the same order (same bits, same test counts, same pushes and pops: the stack bound
+            // stands); only when the wave runs each step changes. lim: the hold clamped to the lanes that entered
+            // this iteration, so a wave whose walking lanes all continue is never held.
+            uint32_t lim = 0u;
+            if constexpr (HOLD) lim = min(hold, (uint32_t)__popcll(__ballot(1)));
+            // A miss leaves BVH_MISS in `node` (all ones, an inline constant: no leaf word — a leaf at 2^27 - 1 would lie
+            // past any sphere buffer; the leaf block skips it, and the pop that follows overwrites it), so "this lane
+            // wants another step" is `node` alone — the loop condition, the hold's count and "held" after the loop —
+            // and no lane mask has to be carried out of the loop.
+            constexpr uint32_t BVH_MISS = 0xFFFFFFFFu;
             if (!(node & BVH_LEAF_BIT)) {
                 bool any;
                 do {
@@ -509,10 +526,13 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                     // node of depth d <= depth - 1 with sp <= d — so the store needs no branch and exec-mask save)
                     if (HRT_PUSH_ALWAYS || both) stack[sp * LS] = far;
                     sp += both ? 1 : 0;
-                    node = any ? near : node;
-                } while (any && !(node & BVH_LEAF_BIT));
+                    node = any ? near : (HOLD ? BVH_MISS : node);
+                    if constexpr (HOLD) {
+                        if ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT))) < lim) break;
+                    }
+                } while ((HOLD || any) && !(node & BVH_LEAF_BIT));
             }
-            if (node & BVH_LEAF_BIT) {
+            if (HOLD ? (int32_t)node < -1 : (node & BVH_LEAF_BIT) != 0u) {
 #ifdef HRT_STAMPS
                 {
                     constexpr uint32_t DIAG_LOW = 24u;
@@ -615,11 +635,15 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
 #endif
                 if constexpr (COUNT) tally.spheres += cnt;
             }
-            if (sp == 0) {
-                finished = 1u;
-                break;
+            // (a held lane — an internal node whose step hit — does not pop and cannot be finished; it counts as
+            // walking in the suspend check, and a suspended Q.node may be that internal node: the entry handles it)
+            if (!(HOLD && !(node & BVH_LEAF_BIT))) {
+                if (sp == 0) {
+                    finished = 1u;
+                    break;
+                }
+                node = stack[(--sp) * LS];
             }
-            node = stack[(--sp) * LS];
             if constexpr (SUSPEND) {
                 if ((uint32_t)__popcll(__ballot(1)) < below) break;
             }
@@ -2909,7 +2933,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     Tally tally;
     uint32_t queries = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
-    const uint32_t suspend_below = P.suspend_below;
+    // (one kernarg word: the suspend threshold in bits 0..7, the descent hold in bits 8..15 — renderer.cpp)
+    const uint32_t suspend_below = P.suspend_below & 0xFFu, hold = P.suspend_below >> 8;
 
     bool drained = false;
     Ray ray;
@@ -3087,7 +3112,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
         HRT_LANES(1, have && qs == 1u);
         if (have && qs == 1u) {
             if constexpr (LNODES) {  // (depth <= LNODE_DEPTH = SPLIT_STACK: no overflow)
-                if (bvh_run<true, SPLIT_STACK, true, true, 256, true, true, COUNT>(P, ray, Q, stack, tally, suspend_below, lnodes))
+                if (bvh_run<true, SPLIT_STACK, true, true, 256, true, true, COUNT, !PACKET>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
                     qs = 2u;
             } else {
                 if (bvh_run<true, SPLIT_STACK, true, true, 256, false, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))

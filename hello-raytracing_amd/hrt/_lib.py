@@ -147,6 +147,7 @@ SIGNATURES = {
 # include/hrt_testing.h: test-only entry points (fault injection), not part of the drop-in surface.
 TESTING_SIGNATURES = {
     "rt_testing_set_faults": (C.c_int, [_P, _U32, _U32]),
+    "rt_testing_set_descent_hold": (C.c_int, [_P, _U32]),
 }
 
 _lib = None

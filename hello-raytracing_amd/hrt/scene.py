@@ -353,6 +353,10 @@ class Renderer:
         """Test-only fault injection (include/hrt_testing.h rt_testing_set_faults)."""
         check(lib().rt_testing_set_faults(self._h, ring_slots_max, fail_alloc_above_mb), "testing_set_faults")
 
+    def set_descent_hold(self, hold: int) -> None:
+        """Test-only: the descent hold of k_trace_split (include/hrt_testing.h rt_testing_set_descent_hold)."""
+        check(lib().rt_testing_set_descent_hold(self._h, hold), "testing_set_descent_hold")
+
     @property
     def local_rows(self) -> int:
         from .parallel import local_rows

@@ -19,6 +19,13 @@ extern "C" {
  * Both stay set until changed; a new renderer starts with both 0. */
 int rt_testing_set_faults(rt_renderer *r, uint32_t ring_slots_max, uint32_t fail_alloc_above_mb);
 
+/* hold: the descent hold of the sphere program's suspendable-walk kernel with LDS nodes (k_trace_split): after a box
+ *   step that fewer than `hold` lanes of a wave would follow with another one, while other walking lanes wait at a
+ *   leaf or a miss, the wave leaves the descent and the stragglers take their next step with the lanes that popped.
+ *   0..64 (RT_ERR_ARG above), 0 = off. Every value draws the same image with the same test counts; only the speed
+ *   changes. Stays set until changed; a new renderer starts with the measured default. */
+int rt_testing_set_descent_hold(rt_renderer *r, uint32_t hold);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,7 @@ struct rt_renderer {
     DevBuf<float> image;
     DevBuf<float4> sph_geo;
     DevBuf<hrt_dev::SphereAux> sph_aux;
+    DevBuf<hrt_dev::SphereAux> code_aux;  // sph_aux in BVH-code order, then in slot order (KParams::code_aux)
     DevBuf<hrt_dev::SpherePair> sph_pairs;
     uint32_t n_spheres = 0;
     // culling BVH over the sphere slots (SCAN_BVH)
@@ -224,7 +225,8 @@ struct rt_renderer {
 
     uint32_t row_block() const { return std::max(params.row_block, 1u); }
     uint64_t device_bytes() const {
-        return image.bytes() + sph_geo.bytes() + sph_aux.bytes() + sph_pairs.bytes() + bvh_nodes.bytes() + bvh_sph.bytes() +
+        return image.bytes() + sph_geo.bytes() + sph_aux.bytes() + code_aux.bytes() + sph_pairs.bytes() + bvh_nodes.bytes() +
+               bvh_sph.bytes() +
                bvh_hnodes.bytes() + bvh_slot.bytes() + bvh_large.bytes() + nodes.bytes() + nodes_so.bytes() + tris.bytes() +
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
@@ -406,8 +408,16 @@ int upload_spheres(rt_renderer* r) {
     const std::vector<float4> bnodes = pack_bvh_nodes(B.nodes, B.root_center);
     const std::vector<uint4> hnodes = pack_bvh_hnodes(B.nodes, B.root_center);
     const size_t nleaf = B.slot.size();
+    // the hit records in BVH-code order (leaf positions, then the large list), then in slot order: k_trace_split
+    // shades its winner by code, and the full-scan fallback's slot indexes the tail (KParams::code_aux)
+    std::vector<hrt_dev::SphereAux> caux;
+    caux.reserve(nleaf + B.large.size() + nslots);
+    for (const int sl : B.slot) caux.push_back(aux[(size_t)sl]);
+    for (const int sl : B.large) caux.push_back(aux[(size_t)sl]);
+    caux.insert(caux.end(), aux.begin(), aux.end());
     int rc = ensure(r->sph_geo, nslots);
     if (!rc) rc = ensure(r->sph_aux, nslots);
+    if (!rc) rc = ensure(r->code_aux, std::max<size_t>(caux.size(), 1));
     if (!rc) rc = ensure(r->sph_pairs, npairs);
     if (!rc) rc = ensure(r->bvh_nodes, bnodes.size());
     if (!rc) rc = ensure(r->bvh_hnodes, hnodes.size());
@@ -418,6 +428,8 @@ int upload_spheres(rt_renderer* r) {
     if (nslots) {
         HIP_TRY(hipMemcpyAsync(r->sph_geo.ptr, geo.data(), nslots * sizeof(float4), hipMemcpyHostToDevice, r->stream));
         HIP_TRY(hipMemcpyAsync(r->sph_aux.ptr, aux.data(), nslots * sizeof(aux[0]), hipMemcpyHostToDevice, r->stream));
+        HIP_TRY(hipMemcpyAsync(r->code_aux.ptr, caux.data(), caux.size() * sizeof(caux[0]), hipMemcpyHostToDevice,
+                               r->stream));
         HIP_TRY(hipMemcpyAsync(r->sph_pairs.ptr, pairs.data(), npairs * sizeof(pairs[0]), hipMemcpyHostToDevice,
                                r->stream));
         HIP_TRY(hipMemcpyAsync(r->bvh_nodes.ptr, bnodes.data(), bnodes.size() * sizeof(float4),
@@ -523,6 +535,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     P.image = r->image.ptr;
     P.sph_geo = r->sph_geo.ptr;
     P.sph_aux = r->sph_aux.ptr;
+    P.code_aux = r->code_aux.ptr;
     P.nodes = r->nodes.ptr;
     P.nodes_so = r->nodes_so.ptr;
     P.so_ok = r->so_ok ? 1u : 0u;
@@ -571,7 +584,8 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     // fp16 boxes reach up to one half ulp (2^-11 relative) past the f32 root box
     P.bvh_rr_h = std::nextafter(B.root_radius * (1.0f + 0x1p-9f), INFINITY);
     P.bvh_nnodes = (uint32_t)B.nodes.size();
-    P.bvh_lnodes = (HRT_LNODES && B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH) ? 1u : 0u;
+    P.bvh_lnodes = (HRT_LNODES && B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH &&
+                    B.large.size() <= hrt_dev::LLARGE_CAP) ? 1u : 0u;  // (the large list in LDS too: LLARGE_CAP)
     // (0 auto = off: the packet walk measured -8 % on C3)
     P.packet = (P.bvh_lnodes && r->params.packet == 2u) ? 1u : 0u;
     // delta = 8u r_max + min(16u D^2 / r_min, 2e-3 D) + 4u D + 4e-23/|d|  (u = 2^-24)
@@ -580,6 +594,13 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     P.pad_k2 = B.r_min > 0.0f ? 16.0f * u / B.r_min : INFINITY;
     P.pad_k3 = 2e-3f;
     P.pad_k4 = 4.0f * u;
+    P.bq_nlarge = P.nlarge;
+    for (int k = 0; k < 3; k++) P.bq_rc[k] = P.bvh_rc[k];
+    P.bq_rr_h = P.bvh_rr_h;
+    P.bq_k1 = P.pad_k1;
+    P.bq_k2 = P.pad_k2;
+    P.bq_k3 = P.pad_k3;
+    P.bq_k4 = P.pad_k4;
     const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
     const uint32_t schedule = resolve_schedule(r, count);
     r->last_variant = variant;
@@ -973,6 +994,7 @@ void delete_buffers(rt_renderer* r) {
     r->image.release();
     r->sph_geo.release();
     r->sph_aux.release();
+    r->code_aux.release();
     r->sph_pairs.release();
     r->bvh_nodes.release();
     r->bvh_sph.release();

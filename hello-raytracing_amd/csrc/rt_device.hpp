@@ -95,6 +95,13 @@ constexpr uint32_t FOLD_MAX_JOBS = 48;
 
 constexpr uint32_t LNODE_CAP = 192;
 constexpr uint32_t LNODE_DEPTH = 8;
+// k_trace_split<LNODES> also keeps the large list's spheres (16 B each) in LDS; longer lists run the other kernel. 14: the
+// kernel's 22,816 B + 224 B = 23,040 B, a multiple of the 512-B LDS allocation granule that still fits 7 workgroups in
+// the CU's 160 KB (16 entries round up to 23,552 B: the seventh workgroup no longer fits, C3 -2.6 %)
+#ifndef HRT_LLARGE_CAP
+#define HRT_LLARGE_CAP 14
+#endif
+constexpr uint32_t LLARGE_CAP = HRT_LLARGE_CAP;
 
 // Camera-derived constants of make_ray / fs_main, read only when primary rays are generated (once per frame
 // block in the sample queue). The kernels read them through kargs() (below), a pointer to the kernarg segment
@@ -204,6 +211,17 @@ struct KParams {
     const float* fold_prev;
     uint32_t* fold_next;
     uint32_t fold_nframes, fold_frame0, fold_mod, pad_f;
+    // the sphere records in BVH-code order (k_trace_split shades its winner by code, no slot lookup): [0, nleaf)
+    // sph_aux[bvh_slot[c]], [nleaf, nleaf + nlarge) sph_aux[large_slots[k]], then the slot-order table again from
+    // nleaf + nlarge on (the full-scan fallback's winner is a slot: one base, an index offset)
+    const SphereAux* code_aux;
+    // k_trace_split<LNODES>'s bvh_begin constants side by side, fetched per query with one wide scalar load (copies of
+    // nlarge, bvh_rc, bvh_rr_h, pad_k1..4 above: the other kernels' kernarg offsets and scalar loads stay as they were)
+    uint32_t bq_nlarge;
+    float bq_rc[3];
+    float bq_rr_h;
+    float bq_k1, bq_k2, bq_k3, bq_k4;
+    uint32_t bq_pad[3];
 };
 
 // KParams in the kernarg segment (constant address space: scalar loads), as a pointer the compiler cannot

@@ -319,15 +319,24 @@ __device__ __forceinline__ int bvh_slot_of(const KParams& P, int code) {
     return (uint32_t)code < P.bvh_nleaf ? P.bvh_slot[code] : P.large_slots[code - (int)P.bvh_nleaf];
 }
 
+template <bool SO, typename RC>
+__device__ __forceinline__ void bvh_slab_k(const Ray& r, BvhQuery& Q, RC rc, float rr, float k1, float k2, float k3, float k4);
 template <bool H16, bool SO>
-__device__ __forceinline__ void bvh_slab(const KParams& P, const Ray& r, BvhQuery& Q);
+__device__ __forceinline__ void bvh_slab(const KParams& P, const Ray& r, BvhQuery& Q) {
+    bvh_slab_k<SO>(r, Q, P.bvh_rc, H16 ? P.bvh_rr_h : P.bvh_rr, P.pad_k1, P.pad_k2, P.pad_k3, P.pad_k4);
+}
 
 // Returns true when the walk has to run (false: bvh_end does the full scan).
 // SO (k_trace_split's sign-ordered box test, box_hit_so): Q.S.lo / hi hold the near / far plane constants instead of
 // the min / max ones (swapped per axis where 1/d < 0).
 // COUNT false (k_trace_split without rt_params.count_tests): no box / sphere test counts (1.3 % of C3's kernel time).
-template <bool H16 = false, bool FAST = false, bool KA = false, bool SO = false, bool COUNT = true>
-__device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float best, BvhQuery& Q, Tally& tally) {
+// LLDS (k_trace_split<LNODES>, with KA): the large list's spheres from the workgroup's LDS copy (lgeo, in list order, at
+// most LLARGE_CAP entries: every lane reads the same entry, a broadcast) instead of two dependent global loads per
+// sphere and query, and the query's constants (KParams: bq_nlarge .. bq_k4, side by side) through kargs(), so the
+// slab's eight arrive with one wide scalar load and one wait.
+template <bool H16 = false, bool FAST = false, bool KA = false, bool SO = false, bool COUNT = true, bool LLDS = false>
+__device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float best, BvhQuery& Q, Tally& tally,
+                                          const float4* lgeo = nullptr) {
     const float a = dot(r.d, r.d);
     const float a4 = 4.0f * a, a2 = 2.0f * a;  // recomputed by bvh_run: fewer registers live across rounds
     Q.sp = 0;
@@ -342,10 +351,27 @@ __device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float 
     const uint32_t nleaf = P.bvh_nleaf;
     float bt = best;
     int bc = -1;
-    const uint32_t nlarge = KA ? kargs()->nlarge : P.nlarge;  // (KA: loaded per query, not held in SGPRs)
+#ifndef HRT_BQ_GROUP
+#define HRT_BQ_GROUP 1
+#endif
+    KPtr K = nullptr;
+    if constexpr (LLDS && HRT_BQ_GROUP) K = kargs();
+    // (KA: loaded per query, not held in SGPRs)
+    const uint32_t nlarge = (LLDS && HRT_BQ_GROUP) ? K->bq_nlarge : KA ? kargs()->nlarge : P.nlarge;
 #ifndef HRT_CAND_T
 #define HRT_CAND_T 2
 #endif
+    if constexpr (LLDS) {
+        static_assert(KA && FAST && HRT_CAND_T >= 2, "k_trace_split's begin");
+        // beats() without the slots: the running winner is a large sphere here (the walk has not run) and the list
+        // is in ascending slot order (host/sphere_bvh.hpp), so an equal t later in the list never wins
+        for (uint32_t k = 0, n = min(nlarge, LLARGE_CAP); k < n; k++) {
+            const float4 g = lgeo[k];
+            const bool cand = sphere_candidate(g, r, a4);
+            const float t = candidate_t(g, r, a4, a2, cand);
+            if (cand && t > 0.0f && t < bt) { bt = t; bc = (int)(nleaf + k); }
+        }
+    } else
     for (uint32_t k = 0; k < nlarge; k++) {  // ascending slots: a later equal t never wins here
         const int i = P.large_slots[k];
         float t;
@@ -362,21 +388,26 @@ __device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float 
     if constexpr (COUNT) tally.spheres += nlarge;
     Q.bt = bt;
     Q.bc = bc;
-    bvh_slab<H16, SO>(P, r, Q);
+    if constexpr (LLDS && HRT_BQ_GROUP) {
+        static_assert(H16, "the side-by-side constants hold the fp16 boxes' radius bound");
+        bvh_slab_k<SO>(r, Q, K->bq_rc, K->bq_rr_h, K->bq_k1, K->bq_k2, K->bq_k3, K->bq_k4);
+    } else {
+        bvh_slab<H16, SO>(P, r, Q);
+    }
     Q.node = P.bvh_root;
     return true;
 }
 
-// The walk's slab constants (bvh_begin)
-template <bool H16, bool SO>
-__device__ __forceinline__ void bvh_slab(const KParams& P, const Ray& r, BvhQuery& Q) {
+// The walk's slab constants (bvh_begin): rc the root box centre, rr the boxes' radius bound, k1..k4 KParams::pad_k1..4
+template <bool SO, typename RC>
+__device__ __forceinline__ void bvh_slab_k(const Ray& r, BvhQuery& Q, RC rc, float rr, float k1, float k2, float k3, float k4) {
     const float a = dot(r.d, r.d);
     // per-query padding: delta >= the distance by which a float-accepted sphere can miss geometrically
-    const f3 op = mk(r.o.x - P.bvh_rc[0], r.o.y - P.bvh_rc[1], r.o.z - P.bvh_rc[2]);
+    const f3 op = mk(r.o.x - rc[0], r.o.y - rc[1], r.o.z - rc[2]);
     const float dl = __builtin_amdgcn_sqrtf(dot(op, op));
-    const float D = dl * 1.001f + (H16 ? P.bvh_rr_h : P.bvh_rr);
+    const float D = dl * 1.001f + rr;
     // the last term bounds 4e-23 / |d| from above: v_rsq_f32 (1 ulp) times 1 + 2.5e-5 (no IEEE division per query)
-    const float delta = P.pad_k1 + fmin_ieee(P.pad_k2 * (D * D), P.pad_k3 * D) + P.pad_k4 * D +
+    const float delta = k1 + fmin_ieee(k2 * (D * D), k3 * D) + k4 * D +
                         4.0001e-23f * __builtin_amdgcn_rsqf(a);
     const float pad = 2.02f * delta;
     Q.S.inv = mk(robust_inv(r.d.x), robust_inv(r.d.y), robust_inv(r.d.z));
@@ -527,10 +558,22 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                     if (HRT_PUSH_ALWAYS || both) stack[sp * LS] = far;
                     sp += both ? 1 : 0;
                     node = any ? near : (HOLD ? BVH_MISS : node);
-                    if constexpr (HOLD) {
-                        if ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT))) < lim) break;
+#ifndef HRT_HOLD_INVB
+#define HRT_HOLD_INVB 1
+#endif
+                    // (HRT_HOLD_INVB: the loop condition is the hold's own ballot — emptied by the hold's verdict, a scalar
+                    // select — handed back as a lane predicate, so the exit mask is that scalar mask inverted and the
+                    // node's sign is compared once per step, not twice)
+                    if constexpr (HOLD && HRT_HOLD_INVB) {
+                        const unsigned long long wants = __builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT));
+                        if (!__builtin_amdgcn_inverse_ballot_w64((uint32_t)__popcll(wants) < lim ? 0ull : wants)) break;
+                    } else {
+                        if constexpr (HOLD) {
+                            if ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT))) < lim) break;
+                        }
+                        if (!((HOLD || any) && !(node & BVH_LEAF_BIT))) break;
                     }
-                } while ((HOLD || any) && !(node & BVH_LEAF_BIT));
+                } while (true);
             }
             if (HOLD ? (int32_t)node < -1 : (node & BVH_LEAF_BIT) != 0u) {
 #ifdef HRT_STAMPS
@@ -637,6 +680,25 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
             }
             // (a held lane — an internal node whose step hit — does not pop and cannot be finished; it counts as
             // walking in the suspend check, and a suspended Q.node may be that internal node: the entry handles it)
+#ifndef HRT_POP_ALWAYS
+#define HRT_POP_ALWAYS 1
+#endif
+            if constexpr (HRT_POP_ALWAYS && HOLD) {  // (k_trace_split's walk; the mixed kernels keep the nested form)
+                // The pop without its branches (as HRT_PUSH_ALWAYS for the push): the entry below the top — entry 0 for an
+                // empty stack: inside the stack, its value discarded — is read by every lane, and the new node and stack
+                // depth are selects (a held lane keeps both; a finished lane leaves with depth 0). One exit test remains
+                // where the nested form saved the exec mask three times ("not held", "sp != 0", the read). Same pops.
+                const bool held = HOLD && !(node & BVH_LEAF_BIT);
+                const bool fin = !held && sp == 0;
+                const int spn = max(sp - 1, 0);
+                const uint32_t top = stack[spn * LS];
+                node = held ? node : top;
+                sp = held ? sp : spn;
+                if (fin) {
+                    finished = 1u;
+                    break;
+                }
+            } else
             if (!(HOLD && !(node & BVH_LEAF_BIT))) {
                 if (sp == 0) {
                     finished = 1u;
@@ -826,9 +888,11 @@ __device__ __forceinline__ f3 div_by_radius3_u(f3 n, float radius, float inv_rad
 
 // The hit record from the hit point p = point_on_ray(o, d, t) (k_trace_split's packet-resolved primary rays carry p
 // instead of the origin; h.t is not read after the record is made). U: the guards as wave-uniform branches.
+// tab (k_trace_split): the record table bi indexes when it is not the slot table (KParams::code_aux); h.id carries bi.
 template <bool U = false>
-__device__ __forceinline__ void sphere_record_p(const KParams& P, const f3 p, const f3 d, int bi, float t, Hit& h) {
-    const SphereAux s = P.sph_aux[bi];
+__device__ __forceinline__ void sphere_record_p(const KParams& P, const f3 p, const f3 d, int bi, float t, Hit& h,
+                                                const SphereAux* __restrict__ tab = nullptr) {
+    const SphereAux s = (tab != nullptr ? tab : P.sph_aux)[bi];
     f3 n = p - mk(s.cx, s.cy, s.cz);
     if constexpr (U) {
         n = div_by_radius3_u(n, s.radius, s.inv_radius);
@@ -1390,7 +1454,8 @@ __device__ __forceinline__ f3 random_on_hemisphere(uint32_t& s, const f3& n) {
 // one final normalize instead of one per arm; every lane still performs exactly its own arm's operations
 // (and RNG draws) in the reference's order, so results are unchanged.
 template <int MODE, bool U = false>  // U (sphere program): the exact sequences' guards as wave-uniform branches
-__device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, const Hit& h) {
+__device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, const Hit& h,
+                                        const SphereAux* __restrict__ tab = nullptr) {  // tab: as sphere_record_p
     const bool lambert = (h.id & 3u) == 1u, metal = (h.id & 3u) == 2u;
     f3 hemi = mk(0.0f, 0.0f, 0.0f);
     if (lambert || metal) hemi = random_on_hemisphere<MODE>(s, h.n);  // 3 draws, both arms
@@ -1400,7 +1465,8 @@ __device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, c
         u = reflect(in, h.n) + h.param * hemi;
     } else if (!lambert) {  // MAT_DIELECTRIC and the default arm
         // ir = front ? 1 / param : param, and reflectance's r0 * r0 for that ir, from the host (DielConsts)
-        const float* dc = (MODE == MODE_SPHERE || (MODE != MODE_TRIS && (h.id & 4u))) ? &P.sph_aux[h.id >> 3].inv_param
+        const SphereAux* __restrict__ aux = tab != nullptr ? tab : P.sph_aux;
+        const float* dc = (MODE == MODE_SPHERE || (MODE != MODE_TRIS && (h.id & 4u))) ? &aux[h.id >> 3].inv_param
                                                                                      : &P.mats[h.id >> 3].inv_param;
         const float ir = h.front ? dc[0] : h.param;
         const float cos_t = fmin_ieee(dot(-r.d, h.n), 1.0f);
@@ -2920,12 +2986,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     static_assert(!PACKET || LNODES, "the packet walk reads the LDS nodes and keeps its stack in one VGPR (depth <= 8)");
     constexpr int MODE = MODE_SPHERE;
     constexpr int SPLIT_STACK = LNODES ? (int)LNODE_DEPTH : 14;
+#ifndef HRT_SHADE_BY_CODE
+#define HRT_SHADE_BY_CODE 1
+#endif
+    // (the packet kernels' block entries carry the winner's slot: they shade from the slot table)
+    constexpr bool SHADE_BY_CODE = HRT_SHADE_BY_CODE && !PACKET;
     const uint32_t lane = threadIdx.x & 63u;
     __shared__ uint32_t bvh_stack[SPLIT_STACK * 256];
     __shared__ uint4 lnodes[LNODES ? 2 * LNODE_CAP : 1];
+#ifndef HRT_LLARGE_LDS
+#define HRT_LLARGE_LDS 1
+#endif
+    // (the packet kernels keep the global large list: their register budget is another; out of this change's scope)
+    constexpr bool LLDS = HRT_LLARGE_LDS && LNODES && !PACKET;
+    __shared__ float4 lgeo[LLDS ? LLARGE_CAP : 1];  // the large list's spheres: (cx, cy, cz, r*r), in list order
     if constexpr (LNODES) {
         const uint32_t nn = 2u * min(P.bvh_nnodes, LNODE_CAP);  // renderer.cpp gates LNODES on the same cap
         for (uint32_t i = threadIdx.x; i < nn; i += 256u) lnodes[i] = P.bvh_hnodes[i];
+        if constexpr (LLDS) {
+            if (threadIdx.x < min(P.nlarge, LLARGE_CAP)) {  // renderer.cpp gates LNODES on nlarge <= LLARGE_CAP
+                lgeo[threadIdx.x] = P.sph_geo[P.large_slots[threadIdx.x]];
+            }
+        }
         __syncthreads();
     }
     __shared__ float4 blk[2 * 256];  // the wave's frame block: (o.xyz, d.x), (d.yz, state bits, ok) per lane
@@ -3103,7 +3185,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
         HRT_LANES(0, have && qs == 0u);
         if (have && qs == 0u) {
             if (bounce < P.bounces) {
-                qs = bvh_begin<true, true, true, true, COUNT>(P, ray, FLT_MAX_REF, Q, tally) ? 1u : 2u;
+                qs = bvh_begin<true, true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : 2u;
             } else {  // bounce cap 0: the sample is the sky colour
                 qs = 3u;
             }
@@ -3137,6 +3219,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
                 if (PACKET && qs == 4u) {  // a primary ray the packet resolved: ray.o is its hit point
                     bi = Q.bc;
                     p = ray.o;
+                } else if constexpr (SHADE_BY_CODE) {
+                    // the winner's record by its BVH code (code_aux: no slot lookup); the rare full scan yields a slot,
+                    // which indexes the slot-order records behind the code-order ones
+                    bi = Q.bc;
+                    if (Q.full_scan != 0u) {
+                        bi = bvh_end<true>(P, ray, Q, best, tally);
+                        bi = bi >= 0 ? bi + (int)(P.bvh_nleaf + kargs()->nlarge) : bi;
+                    } else {
+                        best = Q.bt;
+                    }
+                    p = point_on_ray(ray.o, ray.d, best);
                 } else {
                     bi = bvh_end<true>(P, ray, Q, best, tally);
                     p = point_on_ray(ray.o, ray.d, best);
@@ -3147,8 +3240,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
 #ifndef HRT_UGUARD
 #define HRT_UGUARD 1
 #endif
-                    sphere_record_p<HRT_UGUARD != 0>(P, p, ray.d, bi, best, h);
-                    scatter<MODE, HRT_UGUARD != 0>(P, s, ray, h);
+                    const SphereAux* __restrict__ tab = SHADE_BY_CODE ? P.code_aux : nullptr;
+                    sphere_record_p<HRT_UGUARD != 0>(P, p, ray.d, bi, best, h, tab);
+                    scatter<MODE, HRT_UGUARD != 0>(P, s, ray, h, tab);
                     att = att * mk(h.ar * 0.7f, h.ag * 0.7f, h.ab * 0.7f);
                     bounce++;
                     done = bounce >= P.bounces;

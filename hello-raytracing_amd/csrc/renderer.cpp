@@ -24,6 +24,10 @@
 
 hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_accumulate(const hrt_dev::KParams& P, hipStream_t stream);
+hipError_t hrt_launch_cast(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs, uint32_t n,
+                           void* hits, hipStream_t stream);
+hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
+                                   hipStream_t stream);
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -480,22 +484,17 @@ int resolve_variant(const rt_renderer* r) {
     return r->n_spheres > 8 ? hrt_dev::SCAN_DEFER : hrt_dev::SCAN_SIMPLE;
 }
 
-int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime) {
-    if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before drawing");
+// The scene and camera part of the kernel arguments, shared by the draws (launch_frames) and the ray queries
+// (rt_cast_rays, rt_primary_rays): camera constants, row partition, sphere slots with their culling BVH, the triangle
+// heap and, with tri_bvh, the SAH tree. Uploads what is still missing (the zero slots of an empty sphere scene, the SAH
+// tree on its first use). P arrives zeroed; what only a draw reads or writes (frames, bounces, image, counters,
+// schedule) is the caller's. Without a camera (a cast needs none) P.cam stays zero.
+int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     if (r->mode == RT_MODE_SPHERE && r->sph_geo.ptr == nullptr) {
         int rc = upload_spheres(r);  // empty scene: min_sphere_slots zero slots, like an unwritten buffer
         if (rc) return rc;
     }
-    // RT_RAW_COUNTERS exported words, then the sample queue's fold-ring watchdog (rt_kernels.hip idle_spin)
-    int rc = ensure(r->counter, hrt_dev::COUNTER_WORDS);
-    if (!rc) rc = ensure(r->count_spread, (size_t)hrt_dev::CSPREAD * hrt_dev::CSTRIDE);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(r->counter.ptr, 0, hrt_dev::COUNTER_WORDS * sizeof(unsigned long long), r->stream));
-    HIP_TRY(hipMemsetAsync(r->count_spread.ptr, 0, (size_t)hrt_dev::CSPREAD * hrt_dev::CSTRIDE * sizeof(unsigned long long),
-                           r->stream));
-
-    hrt_dev::KParams P{};
-    {
+    if (r->has_camera) {
         hrt_dev::CamDev& cd = P.cam;
         const hrt::Camera& c = r->camera;
         const float* cam = &c.eye.x;
@@ -519,9 +518,6 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     }
     P.W = r->width;
     P.H = r->height;
-    P.dtime = dtime;
-    P.bounces = r->params.bounces;
-    P.ema_cap = (float)r->params.ema_cap;
     P.nslots = r->mode == RT_MODE_TRIS ? 0u : r->n_spheres;
     P.npairs = (P.nslots + 1) / 2;
     P.sph_pairs = r->sph_pairs.ptr;
@@ -532,19 +528,17 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     P.row_block = r->row_block();
     P.row_stride = r->params.row_step * P.row_block;
     P.nrows = r->local_rows();
-    P.image = r->image.ptr;
     P.sph_geo = r->sph_geo.ptr;
     P.sph_aux = r->sph_aux.ptr;
     P.code_aux = r->code_aux.ptr;
     P.nodes = r->nodes.ptr;
     P.nodes_so = r->nodes_so.ptr;
     P.so_ok = r->so_ok ? 1u : 0u;
-    P.count_tests = r->params.count_tests;
     P.tris = r->tris.ptr;
     P.tri_geo = r->tri_geo.ptr;
     P.tri_bvh = (r->mode != RT_MODE_SPHERE && r->params.tri_bvh) ? 1u : 0u;
     if (P.tri_bvh) {
-        rc = upload_tri_tree(r);
+        int rc = upload_tri_tree(r);
         if (rc) return rc;
         P.tb_hnodes = r->tb_hnodes.ptr;
         P.tb_rr_h = std::nextafter(r->tri_tree.root_radius * (1.0f + 0x1p-9f), INFINITY);
@@ -554,22 +548,6 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         P.tb_rr = r->tri_tree.root_radius;
     }
     P.mats = r->mats.ptr;
-    P.counter = r->counter.ptr;
-    P.count_spread = r->count_spread.ptr;
-#ifdef HRT_STAMPS
-    {
-        // k_render's waves, or the persistent kernels' (at most steal_cap = 32 per CU)
-        const size_t wave_words = 8ull * std::max<size_t>((size_t)((r->width + 15u) / 16u) * ((P.nrows + 15u) / 16u) * 4u,
-                                                          32ull * std::max(r->cus, 1u));
-        const size_t words = wave_words + (1ull << 21);  // + one word per job (k_trace's job_trace)
-        int rc2 = ensure(r->wave_trace, words);
-        if (rc2) return rc2;
-        HIP_TRY(hipMemsetAsync(r->wave_trace.ptr, 0, words * sizeof(unsigned long long), r->stream));
-        r->wave_trace_words = words;
-        P.wave_trace = r->wave_trace.ptr;
-        P.job_trace = r->wave_trace.ptr + wave_words;
-    }
-#endif
     const hrt::SphereBvh& B = r->bvh_host;
     P.bvh_nodes = r->bvh_nodes.ptr;
     P.bvh_sph = r->bvh_sph.ptr;
@@ -601,6 +579,42 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
     P.bq_k2 = P.pad_k2;
     P.bq_k3 = P.pad_k3;
     P.bq_k4 = P.pad_k4;
+    return RT_OK;
+}
+
+int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime) {
+    if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before drawing");
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    // RT_RAW_COUNTERS exported words, then the sample queue's fold-ring watchdog (rt_kernels.hip idle_spin)
+    rc = ensure(r->counter, hrt_dev::COUNTER_WORDS);
+    if (!rc) rc = ensure(r->count_spread, (size_t)hrt_dev::CSPREAD * hrt_dev::CSTRIDE);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(r->counter.ptr, 0, hrt_dev::COUNTER_WORDS * sizeof(unsigned long long), r->stream));
+    HIP_TRY(hipMemsetAsync(r->count_spread.ptr, 0, (size_t)hrt_dev::CSPREAD * hrt_dev::CSTRIDE * sizeof(unsigned long long),
+                           r->stream));
+    P.dtime = dtime;
+    P.bounces = r->params.bounces;
+    P.ema_cap = (float)r->params.ema_cap;
+    P.image = r->image.ptr;
+    P.count_tests = r->params.count_tests;
+    P.counter = r->counter.ptr;
+    P.count_spread = r->count_spread.ptr;
+#ifdef HRT_STAMPS
+    {
+        // k_render's waves, or the persistent kernels' (at most steal_cap = 32 per CU)
+        const size_t wave_words = 8ull * std::max<size_t>((size_t)((r->width + 15u) / 16u) * ((P.nrows + 15u) / 16u) * 4u,
+                                                          32ull * std::max(r->cus, 1u));
+        const size_t words = wave_words + (1ull << 21);  // + one word per job (k_trace's job_trace)
+        int rc2 = ensure(r->wave_trace, words);
+        if (rc2) return rc2;
+        HIP_TRY(hipMemsetAsync(r->wave_trace.ptr, 0, words * sizeof(unsigned long long), r->stream));
+        r->wave_trace_words = words;
+        P.wave_trace = r->wave_trace.ptr;
+        P.job_trace = r->wave_trace.ptr + wave_words;
+    }
+#endif
     const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
     const uint32_t schedule = resolve_schedule(r, count);
     r->last_variant = variant;
@@ -1314,6 +1328,49 @@ int rt_draw_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtim
     int rc = launch_frames(r, count, time0, dtime);
     if (!rc) r->time = time0 + (count - 1) * dtime;
     return rc;
+}
+
+// Ray queries (include/hrt.h): the scene as a tiles draw would see it (scene_params: variant, tri_bvh, min_sphere_slots),
+// none of the draw's state — no image, counters, stats, frame count or cost order is read or written.
+int rt_cast_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev, uint32_t n, void* hits_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_cast_rays: null");
+    if (n == 0) return RT_OK;
+    if (!origins_dev || !dirs_dev || !hits_dev) return fail(RT_ERR_ARG, "rt_cast_rays: null buffer");
+    if ((uintptr_t)hits_dev % 16u || (uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_cast_rays: hits must be 16-byte aligned, origins and directions 4-byte aligned");
+    static_assert(sizeof(rt_hit) == 32, "rt_hit: two 16-byte stores per record (k_cast_rays)");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
+    HIP_TRY(hrt_launch_cast(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev, n, hits_dev, r->stream));
+    return RT_OK;
+}
+
+int rt_primary_rays(rt_renderer* r, uint32_t time, void* origins_dev, void* dirs_dev, size_t n_rays) {
+    if (!r) return fail(RT_ERR_ARG, "rt_primary_rays: null");
+    if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before rt_primary_rays");
+    if (n_rays != (size_t)r->local_rows() * r->width)
+        return fail(RT_ERR_ARG, "rt_primary_rays: n_rays must be local_rows x width");
+    if (n_rays == 0) return RT_OK;
+    if (!origins_dev || !dirs_dev) return fail(RT_ERR_ARG, "rt_primary_rays: null buffer");
+    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_primary_rays: origins and directions must be 4-byte aligned");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, (float*)origins_dev, (float*)dirs_dev, r->stream));
+    return RT_OK;
+}
+
+int rt_get_stream(const rt_renderer* r, void** hip_stream) {
+    if (!r || !hip_stream) return fail(RT_ERR_ARG, "rt_get_stream: null");
+    *hip_stream = (void*)r->stream;
+    return RT_OK;
 }
 
 int rt_read_image(rt_renderer* r, float* out, size_t n_floats) {

@@ -1399,7 +1399,7 @@ __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, flo
 
 template <int MODE, int SCAN, bool TSAH = false, bool U = false>  // U: sphere_record_p<U>
 __device__ __forceinline__ bool closest_hit(const KParams& P, const Ray& r, Hit& h, void* lds, Tally& tally,
-                                            uint32_t* tri_cand, uint32_t* tri_stack) {
+                                            uint32_t* tri_cand, uint32_t* tri_stack, int* tri_out = nullptr) {
     float best = FLT_MAX_REF;
     int bi = -1, bj = -1;  // winning sphere slot / triangle index
     if (MODE != MODE_TRIS) {
@@ -1420,6 +1420,7 @@ __device__ __forceinline__ bool closest_hit(const KParams& P, const Ray& r, Hit&
     }
     // every accepted t is < FLT_MAX_REF, so `abs(hit.t - FLT_MAX) < EPSILON` (shader_sphere.wgsl:235) is
     // "nothing accepted"
+    if (tri_out != nullptr) *tri_out = bj;  // (k_cast_rays: the winning triangle's index; the draws pass none)
     if (bj >= 0) {
         tri_record(P, r, P.tris[bj], best, h);
         return true;
@@ -2530,6 +2531,54 @@ __global__ __launch_bounds__(256) void k_render(const KParams P) {
         for (int off = 32; off > 0; off >>= 1) sums[c] += __shfl_xor(sums[c], off);
     }
     if (lane == 0) flush_counts(sums);
+}
+
+// Closest-hit queries for the caller's rays (rt_cast_rays): one ray per lane, the query k_render runs per bounce —
+// closest_hit with the same per-lane lists, FLT_MAX_REF start and tie rules — and one 32-byte record per ray (include/hrt.h
+// rt_hit) as two 16-B stores. Origins and directions are packed 3 x f32 (12-B stride). Reads the scene only: no image,
+// no counters (the Tally is dropped). KParams stays the first argument: closest_hit reads through kargs().
+// Grid: ceil(n / 256) workgroups of 256 (lane_lists sizes its lists for 256 lanes).
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) void k_cast_rays(const KParams P, const float* __restrict__ origins,
+                                                   const float* __restrict__ dirs, uint32_t n, uint4* __restrict__ hits) {
+    const LaneLists lists = lane_lists<MODE, SCAN>();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float* const po = origins + (size_t)i * 3u;
+    const float* const pd = dirs + (size_t)i * 3u;
+    Ray ray;
+    ray.o = mk(po[0], po[1], po[2]);
+    ray.d = mk(pd[0], pd[1], pd[2]);
+    Tally tally;
+    Hit h;
+    int tri = -1;
+    const bool hit = closest_hit<MODE, SCAN, TSAH>(P, ray, h, lists.sphere, tally, lists.tri, lists.tri, &tri);
+    uint4 lo = {__float_as_uint(FLT_MAX_REF), 0xFFFFFFFFu, 0u, 0u}, hi = {0u, 0u, 0u, 0u};  // miss: t, prim -1, zeros
+    if (hit) {
+        const bool sphere = MODE == MODE_SPHERE || (MODE == MODE_MIXED && (h.id & 4u) != 0u);
+        lo = uint4{__float_as_uint(h.t), sphere ? h.id >> 3 : (uint32_t)tri, __float_as_uint(h.n.x), __float_as_uint(h.n.y)};
+        hi = uint4{__float_as_uint(h.n.z), (h.front ? 1u : 0u) | (sphere ? 0u : 2u), h.id >> 3, 0u};
+    }
+    hits[(size_t)i * 2u] = lo;
+    hits[(size_t)i * 2u + 1u] = hi;
+}
+
+// The primary rays of one frame (rt_primary_rays): lane i is pixel (i % W, local row i / W) and stores the origin and
+// direction primary_ray<MODE> gives k_render for that pixel in the frame drawn at `time` (jitter, lens offset and, in the
+// triangle and mixed programs, the normalised direction included), packed 3 x f32. Grid: ceil(nrows W / 256) x 256.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_primary_rays(const KParams P, uint32_t time, float* __restrict__ origins,
+                                                      float* __restrict__ dirs) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)P.nrows * P.W) return;
+    const uint32_t kr = (uint32_t)(i / P.W), x = (uint32_t)(i - (size_t)kr * P.W);
+    const uint32_t y = global_row(P.row0, P.row_block, P.row_stride, kr);
+    uint32_t s = 0;
+    const Ray ray = primary_ray<MODE>(&kargs()->cam, x, y, time, s);
+    float* const po = origins + i * 3u;
+    float* const pd = dirs + i * 3u;
+    po[0] = ray.o.x; po[1] = ray.o.y; po[2] = ray.o.z;
+    pd[0] = ray.d.x; pd[1] = ray.d.y; pd[2] = ray.d.z;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -4212,6 +4261,56 @@ hipError_t hrt_launch_render(int mode, int variant, const KParams& P, hipStream_
         if (P.tri_bvh) launch_render_mode<MODE_MIXED, true>(variant, P, grid, block, stream);
         else launch_render_mode<MODE_MIXED, false>(variant, P, grid, block, stream);
         break;
+    }
+    return hipGetLastError();
+}
+
+// Host-side launcher of rt_cast_rays: the (MODE, SCAN, TSAH) set of the tiles schedule (launch_render_mode), one ray
+// per lane. (No kname: rt_stats.kernel names the last draw's kernel.)
+template <int MODE, bool TSAH>
+static void launch_cast_mode(int variant, const KParams& P, const float* origins, const float* dirs, uint32_t n, uint4* hits,
+                             dim3 grid, dim3 block, hipStream_t stream) {
+    if constexpr (MODE == MODE_TRIS) {
+        hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
+    } else {
+        if (variant == SCAN_SIMPLE)
+            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
+        else if (variant == SCAN_DEFER)
+            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
+        else
+            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
+    }
+}
+
+hipError_t hrt_launch_cast(int mode, int variant, const KParams& P, const float* origins, const float* dirs, uint32_t n,
+                           void* hits, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    dim3 block(256);
+    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
+    uint4* const h = (uint4*)hits;
+    switch (mode) {
+    case MODE_SPHERE: launch_cast_mode<MODE_SPHERE, false>(variant, P, origins, dirs, n, h, grid, block, stream); break;
+    case MODE_TRIS:
+        if (P.tri_bvh) launch_cast_mode<MODE_TRIS, true>(variant, P, origins, dirs, n, h, grid, block, stream);
+        else launch_cast_mode<MODE_TRIS, false>(variant, P, origins, dirs, n, h, grid, block, stream);
+        break;
+    default:
+        if (P.tri_bvh) launch_cast_mode<MODE_MIXED, true>(variant, P, origins, dirs, n, h, grid, block, stream);
+        else launch_cast_mode<MODE_MIXED, false>(variant, P, origins, dirs, n, h, grid, block, stream);
+        break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t hrt_launch_primary_rays(int mode, const KParams& P, uint32_t time, float* origins, float* dirs, hipStream_t stream) {
+    const unsigned long long n = (unsigned long long)P.nrows * P.W;
+    if (n == 0) return hipSuccess;
+    dim3 block(256);
+    dim3 grid((uint32_t)((n + 255u) / 256u));
+    switch (mode) {
+    case MODE_SPHERE: hipLaunchKernelGGL((k_primary_rays<MODE_SPHERE>), grid, block, 0, stream, P, time, origins, dirs); break;
+    case MODE_TRIS: hipLaunchKernelGGL((k_primary_rays<MODE_TRIS>), grid, block, 0, stream, P, time, origins, dirs); break;
+    default: hipLaunchKernelGGL((k_primary_rays<MODE_MIXED>), grid, block, 0, stream, P, time, origins, dirs); break;
     }
     return hipGetLastError();
 }

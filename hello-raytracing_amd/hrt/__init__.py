@@ -4,9 +4,9 @@ The compute path is lib/libhrt.so (HIP kernels for gfx950 behind the C-ABI of in
 package is the host-side mirror of the reference's Rust scene API plus ctypes plumbing.
 """
 from . import _lib
-from ._lib import (UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
+from ._lib import (RT_HIT_FRONT, RT_HIT_TRIANGLE, RT_T_MISS, UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
                    lib)
-from .scene import (CAMERA_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
+from .scene import (CAMERA_DTYPE, HIT_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
                     Renderer, SceneSphere, SceneTris, Sphere, Tree, Vec3, compare_ppm_images, f32,
                     ppm_from_image, read_asset, render_ppm, spheres_array)
@@ -30,6 +30,7 @@ def check_uniform_guards(n_waves: int, seed: int) -> dict:
 
 
 __all__ = [
+    "HIT_DTYPE", "RT_HIT_FRONT", "RT_HIT_TRIANGLE", "RT_T_MISS",
     "LIB_PATH", "RT_FOLD_AUTO", "RT_FOLD_BUFFER", "RT_FOLD_NEXT", "RT_FOLD_RING", "RT_MODE_MIXED", "RT_SCHEDULE_AUTO", "RT_SCHEDULE_QUEUE", "RT_SCHEDULE_TILES", "RT_MODE_SPHERE", "RT_MODE_TRIS", "RtError", "RtParams", "RtStats", "lib",
     "CAMERA_DTYPE", "DIELECTRIC", "LAMBERTIAN", "MATERIAL_DTYPE", "MAX_OBJECT_IN_SCENE", "METAL", "NODE_DTYPE",
     "PI", "SPHERE_DTYPE", "TRIANGLE_DTYPE", "Camera", "ComparisonError", "Material", "Mesh", "OrbitCamera", "Renderer",

@@ -28,6 +28,10 @@ RT_MODE_TRIS = 1
 RT_MODE_MIXED = 2
 RT_SCHEDULE_AUTO, RT_SCHEDULE_TILES, RT_SCHEDULE_QUEUE = 0, 1, 2
 RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_RING, RT_FOLD_NEXT = 0, 1, 2, 3
+# ray queries (include/hrt.h rt_hit, rt_cast_rays)
+RT_T_MISS = 3.40282e+38  # (the header's f32 literal: compare with numpy.float32(RT_T_MISS))
+RT_HIT_FRONT = 1
+RT_HIT_TRIANGLE = 2
 # rt_check_uniform_guards: out[helper * RT_UGUARD_WORDS + column] (include/hrt.h)
 UGUARD_HELPERS = ("sqrt_exact_u", "normalize_exact_u", "candidate_t", "div_by_radius3_u", "div_by_len_rng_u",
                   "div_cam_u")
@@ -105,6 +109,9 @@ SIGNATURES = {
     "rt_get_frame_count": (C.c_int, [_P, _PU32]),
     "rt_draw": (C.c_int, [_P]),
     "rt_draw_frames": (C.c_int, [_P, _U32, _U32, _U32]),
+    "rt_cast_rays": (C.c_int, [_P, _P, _P, _U32, _P]),
+    "rt_primary_rays": (C.c_int, [_P, _U32, _P, _P, C.c_size_t]),
+    "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),
     "rt_write_image": (C.c_int, [_P, _PF, C.c_size_t]),
     "rt_copy_image_to_device": (C.c_int, [_P, _P, C.c_size_t]),

@@ -42,6 +42,10 @@ SPHERE_DTYPE = np.dtype([("center", "<f4", 3), ("radius", "<f4"), ("material", M
 NODE_DTYPE = np.dtype([("bound_min", "<f4", 4), ("bound_max", "<f4", 4)])
 TRIANGLE_DTYPE = np.dtype([("a", "<f4", 4), ("b", "<f4", 4), ("c", "<f4", 4), ("custom", "<f4", 3),
                            ("material", "<u4")])
+# rt_hit (include/hrt.h): one record of rt_cast_rays
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("n", "<f4", 3), ("flags", "<u4"), ("material", "<u4"),
+                      ("reserved", "<u4")])
+assert HIT_DTYPE.itemsize == 32
 assert CAMERA_DTYPE.itemsize == 80 and MATERIAL_DTYPE.itemsize == 32 and SPHERE_DTYPE.itemsize == 48
 assert NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 64
 
@@ -376,6 +380,77 @@ class Renderer:
 
     def copy_image_to_device(self, dst_ptr: int, n_floats: int) -> None:
         check(lib().rt_copy_image_to_device(self._h, C.c_void_p(dst_ptr), n_floats), "copy_image_to_device")
+
+    # --- ray queries (include/hrt.h rt_cast_rays / rt_primary_rays; torch is imported on first use)
+    def _torch_device(self):
+        import torch
+
+        return torch.device("cuda", self.device()[0])
+
+    def _rays_on_device(self, a, what: str):
+        """(N, 3) float32 rays as a contiguous tensor on the renderer's device (numpy arrays are uploaded)."""
+        import torch
+
+        dev = self._torch_device()
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        if a.dtype != torch.float32 or a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"cast_rays: {what} must be (N, 3) float32, got {tuple(a.shape)} {a.dtype}")
+        if a.device != dev:
+            raise ValueError(f"cast_rays: {what} is on {a.device}, the renderer draws on {dev}")
+        return a.contiguous()
+
+    def stream(self) -> int:
+        """The renderer's HIP stream as an integer handle (rt_get_stream), e.g. for torch.cuda.ExternalStream."""
+        s = C.c_void_p()
+        check(lib().rt_get_stream(self._h, C.byref(s)), "rt_get_stream")
+        return int(s.value or 0)
+
+    def cast_rays(self, origins, dirs) -> dict:
+        """rt_cast_rays: the closest hit of each ray, as one bounce of the renderer's program would find it. origins and
+        dirs: (N, 3) float32, torch tensors on the renderer's device or numpy arrays. Returns torch tensors on that
+        device: t (N,) float32 (RT_T_MISS for a miss), prim (N,) int32 (-1 for a miss), normal (N, 3) float32, and
+        flags (RT_HIT_FRONT | RT_HIT_TRIANGLE) and material as (N,) int32. Synchronises torch's current stream before
+        the call and the renderer after it."""
+        import torch
+
+        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError(f"cast_rays: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
+        n = int(o.shape[0])
+        if n >= 1 << 32:
+            raise ValueError("cast_rays: at most 2^32 - 1 rays per call")
+        dev = self._torch_device()
+        hits = torch.empty((n, HIT_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_cast_rays(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), n,
+                                 C.c_void_p(hits.data_ptr())), "cast_rays")
+        self.synchronize()
+        f = hits.view(torch.float32)
+        return {"t": f[:, 0].clone(), "prim": hits[:, 1].clone(), "normal": f[:, 2:5].clone(),
+                "flags": hits[:, 5].clone(), "material": hits[:, 6].clone()}
+
+    def primary_rays(self, time: int):
+        """rt_primary_rays: (origins, dirs), each (local_rows, width, 3) float32 on the renderer's device — the rays the
+        frame drawn at `time` traces first for each of this renderer's pixels."""
+        import torch
+
+        dev = self._torch_device()
+        shape = (self.local_rows, self.width, 3)
+        o = torch.empty(shape, dtype=torch.float32, device=dev)
+        d = torch.empty(shape, dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_primary_rays(self._h, int(time) & 0xFFFFFFFF, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                    shape[0] * shape[1]), "primary_rays")
+        self.synchronize()
+        return o, d
+
+    def first_hit(self, time: int) -> dict:
+        """The first hit behind each pixel sample of the frame drawn at `time` (depth, normal, primitive and material
+        guide buffers): cast_rays on primary_rays, shaped (local_rows, width[, 3])."""
+        o, d = self.primary_rays(time)
+        hit = self.cast_rays(o.view(-1, 3), d.view(-1, 3))
+        return {k: v.view(*o.shape[:2], *v.shape[1:]) for k, v in hit.items()}
 
     def stats(self) -> RtStats:
         s = RtStats()

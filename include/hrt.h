@@ -235,6 +235,42 @@ int rt_get_stats(const rt_renderer *r, rt_stats *out);
  * either, but the reference has no per-sample buffer). */
 int rt_release_scratch(rt_renderer *r);
 
+/* ---- ray queries (no reference counterpart: the reference traces only the rays fs_main makes for itself) ----
+ * The closest-hit query of the render path — the sphere culling BVH or linear scans, the reference heap walk with its
+ * 600-step cap, the opt-in SAH tree — for rays the caller keeps in device memory, and the primary rays a frame samples.
+ * Neither call reads or changes the image, the frame count, rt_get_stats, the raw counters or the learnt cost order. */
+#define RT_T_MISS 3.40282e+38f      /* the WGSL FLT_MAX: t of a ray that hit nothing */
+#define RT_HIT_FRONT    1u          /* Hit.front as the running program computes it   */
+#define RT_HIT_TRIANGLE 2u          /* prim indexes the triangle buffer, else a sphere slot */
+typedef struct rt_hit {             /* 32 B */
+    float t; int32_t prim;          /* miss: RT_T_MISS, -1, everything below 0 */
+    float n[3];                     /* Hit.n of the render path (sphere: faced against the ray; triangle: as stored) */
+    uint32_t flags, material, reserved; /* material: sphere slot, or Triangle.material */
+} rt_hit;
+/* n rays -> n rt_hit records. origins_dev / dirs_dev: n x 3 f32 each, packed (12-byte stride, 4-byte aligned);
+ * hits_dev: n x 32 B, 16-byte aligned. All three are device memory on the renderer's GPU. Asynchronous on the renderer's
+ * stream: rt_synchronize waits for it, and the caller orders its own streams against it (the buffers must be ready
+ * before the call, and are not to be read before rt_synchronize).
+ * The hit is exactly what one bounce of trace() would see for that ray in the renderer's program:
+ *   - sphere program: d is not normalised, so t is in units of |d|; the near root only, t > 0;
+ *   - triangle and mixed programs: triangles accept t >= 1e-4, and a triangle replaces a sphere only with a smaller t;
+ *   - the reference heap walk keeps its 600-step cap (it may miss what the cap cuts off) unless tri_bvh = 1;
+ *   - zero-filled padding slots (rt_params.min_sphere_slots) count as spheres of radius 0 at the origin.
+ * rt_params.variant (0 = auto by slot count), tri_bvh and min_sphere_slots apply as in a tiles draw; the schedule, fold,
+ * steal and cost-order knobs do not. n = 0 returns RT_OK and launches nothing; n > 0 with a null pointer is RT_ERR_ARG. A
+ * scene state in which a draw fails gives the same status here; no camera is needed. */
+int rt_cast_rays(rt_renderer *r, const void *origins_dev, const void *dirs_dev, uint32_t n, void *hits_dev);
+/* The primary rays of the frame drawn at `time` (rt_set_time): for local row k and column x, ray k * width + x is the one
+ * fs_main traces for that pixel — antialiasing jitter, lens offset and, in the triangle and mixed programs, the
+ * normalised direction included — as 3 f32 origin and 3 f32 direction, packed like rt_cast_rays' inputs (device memory,
+ * asynchronous on the renderer's stream). Needs a camera (RT_ERR_STATE otherwise, as drawing does); n_rays must equal
+ * local_rows x width (RT_ERR_ARG otherwise). rt_cast_rays on them gives the first hit behind each pixel sample. */
+int rt_primary_rays(rt_renderer *r, uint32_t time, void *origins_dev, void *dirs_dev, size_t n_rays);
+/* The renderer's HIP stream (a hipStream_t, created non-blocking; owned by the renderer, valid until rt_destroy): for a
+ * caller that orders its own streams against the asynchronous calls above with events instead of rt_synchronize, or
+ * times them (scripts/bench_cast.py). */
+int rt_get_stream(const rt_renderer *r, void **hip_stream);
+
 /* Test-only entry points (fault injection) are declared in hrt_testing.h, not here: they are not part of
  * the drop-in surface. */
 
@@ -304,7 +340,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
  * / rt_get_stats copy this header's sizes. A caller built against another header checks *version == RT_ABI_VERSION (or
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
-                             5: rt_params.cost_order, rt_stats.ordered_launches */
+                             5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream came
+                             later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

@@ -562,8 +562,9 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     // fp16 boxes reach up to one half ulp (2^-11 relative) past the f32 root box
     P.bvh_rr_h = std::nextafter(B.root_radius * (1.0f + 0x1p-9f), INFINITY);
     P.bvh_nnodes = (uint32_t)B.nodes.size();
+    // (the large list in LDS too: LLARGE_CAP; the leaf spheres: a leaf word in a 16-bit walk-stack entry)
     P.bvh_lnodes = (HRT_LNODES && B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH &&
-                    B.large.size() <= hrt_dev::LLARGE_CAP) ? 1u : 0u;  // (the large list in LDS too: LLARGE_CAP)
+                    B.large.size() <= hrt_dev::LLARGE_CAP && B.slot.size() <= hrt_dev::LNODE_LEAF_SPHERES) ? 1u : 0u;
     // (0 auto = off: the packet walk measured -8 % on C3)
     P.packet = (P.bvh_lnodes && r->params.packet == 2u) ? 1u : 0u;
     // delta = 8u r_max + min(16u D^2 / r_min, 2e-3 D) + 4u D + 4e-23/|d|  (u = 2^-24)

@@ -95,6 +95,10 @@ constexpr uint32_t FOLD_MAX_JOBS = 48;
 
 constexpr uint32_t LNODE_CAP = 192;
 constexpr uint32_t LNODE_DEPTH = 8;
+// leaf spheres an LNODES tree may hold: k_trace_split<LNODES>'s 16-bit walk-stack entries keep a leaf word's
+// first << 4 | count in 15 bits (renderer.cpp's gate; BVH_MAX_LEAF: the builder's leaf size, host/sphere_bvh.hpp)
+constexpr uint32_t LNODE_LEAF_SPHERES = 2047;
+constexpr uint32_t BVH_MAX_LEAF = 4;
 // k_trace_split<LNODES> also keeps the large list's spheres (16 B each) in LDS; longer lists run the other kernel. 14: the
 // kernel's 22,816 B + 224 B = 23,040 B, a multiple of the 512-B LDS allocation granule that still fits 7 workgroups in
 // the CU's 160 KB (16 entries round up to 23,552 B: the seventh workgroup no longer fits, C3 -2.6 %)

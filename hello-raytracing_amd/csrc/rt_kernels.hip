@@ -469,13 +469,17 @@ __device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz
 // pending sibling per level above it), so a push at an internal node (d <= depth - 1) leaves at most depth. The
 // push then needs no bound check and the walk no overflow flag (5 VALU of a ~50-VALU box step).
 // SO (with H16; Q from bvh_begin<.., SO>): box_hit_so.
+// SW: the stack's entry type, uint32_t or (k_trace_split<LNODES>: HOLD, child words sign-extended from 16 bits, `hn` holds
+// them so) int16_t: the push stores the low half, the pop sign-extends it back.
 template <bool SUSPEND, int STACK = BVH_STACK, bool SELECT = false, bool H16 = false, uint32_t LS = 256,
-          bool NOOVF = false, bool SO = false, bool COUNT = true, bool HOLD = false>
-__device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery& Q, uint32_t* stack,
+          bool NOOVF = false, bool SO = false, bool COUNT = true, bool HOLD = false, typename SW = uint32_t>
+__device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery& Q, SW* stack,
                                         Tally& tally, uint32_t below, const uint4* __restrict__ hn = nullptr,
                                         uint32_t hold = 0u) {
     static_assert(!SO || H16, "the sign-ordered box test reads fp16 pairs");
     static_assert(!HOLD || (NOOVF && SO && HRT_BTEST), "the descent hold lives in the bottom-tested descent loop");
+    constexpr bool S16 = sizeof(SW) == 2;
+    static_assert(!S16 || HOLD, "16-bit entries: k_trace_split<LNODES>'s walk only");
     const float4* __restrict__ nodes = P.bvh_nodes;
     const Slab S = Q.S;
     // SO: the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds)
@@ -555,7 +559,7 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                     // (HRT_PUSH_ALWAYS: the far child is written whether or not it is pushed — one slot past the top
                     // when it is not, never read since sp does not advance, and inside the stack: a box step runs at a
                     // node of depth d <= depth - 1 with sp <= d — so the store needs no branch and exec-mask save)
-                    if (HRT_PUSH_ALWAYS || both) stack[sp * LS] = far;
+                    if (HRT_PUSH_ALWAYS || both) stack[sp * LS] = (SW)far;
                     sp += both ? 1 : 0;
                     node = any ? near : (HOLD ? BVH_MISS : node);
 #ifndef HRT_HOLD_INVB
@@ -588,7 +592,8 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                     }
                 }
 #endif
-                const uint32_t first = (node >> 4) & 0x07FFFFFFu, cnt = node & 15u;
+                // (S16: a leaf word is sign-extended from bit 15 — from the LDS nodes or popped — or the root word as built)
+                const uint32_t first = (node >> 4) & (S16 ? 0x7FFu : 0x07FFFFFFu), cnt = node & 15u;
 #if HRT_LEAF_DEFER
                 if constexpr (SELECT) {
                     // Two passes over the leaf (k_trace_split): the cheap discriminant test of every sphere first, the
@@ -691,7 +696,7 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                 const bool held = HOLD && !(node & BVH_LEAF_BIT);
                 const bool fin = !held && sp == 0;
                 const int spn = max(sp - 1, 0);
-                const uint32_t top = stack[spn * LS];
+                const uint32_t top = (uint32_t)(int32_t)stack[spn * LS];  // (S16: a sign-extending 16-bit read)
                 node = held ? node : top;
                 sp = held ? sp : spn;
                 if (fin) {
@@ -704,7 +709,7 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                     finished = 1u;
                     break;
                 }
-                node = stack[(--sp) * LS];
+                node = (uint32_t)(int32_t)stack[(--sp) * LS];
             }
             if constexpr (SUSPEND) {
                 if ((uint32_t)__popcll(__ballot(1)) < below) break;
@@ -1814,16 +1819,36 @@ struct WaveJobs {
     __device__ uint32_t cur() const { return (get(WJ_FLAGS) >> WJ_CUR_SHIFT) & 3u; }
 };
 
+// The fold mode (KParams::ring_mode: the sample buffer or the fold ring) is a template parameter of the sample-queue
+// kernels' bodies (trace_queue, trace_split, trace_split_tris: one kernel per mode, k_trace* and k_ring*) and of the
+// helpers below that differ by it (RING; the launchers pick by P.ring_mode), so a sample-buffer kernel holds none of
+// the ring's code and reads no mode word: every bench configuration draws with the sample buffer,
+// and k_trace_split paid for the ring with about six scalar-load round trips of ring_mode per round (DESIGN.md §4
+// Round 9). The helpers take it as an int: 0, 1, or FOLD_DYN, the mode tested at run time as before round 9 — the packet
+// kernels (their register budget is another; the ring + counting one spilled when specialised), and every kernel with
+// HRT_FOLD_TEMPLATE 0 (A/B builds).
+#ifndef HRT_FOLD_TEMPLATE
+#define HRT_FOLD_TEMPLATE 1
+#endif
+constexpr int FOLD_DYN = 2;
+template <int RING>
+__device__ __forceinline__ bool fold_ring() {
+    if constexpr (HRT_FOLD_TEMPLATE && RING != FOLD_DYN) return RING != 0;
+    else return kargs()->ring_mode != 0u;
+}
+
 // A dealt sample's job reference (`fl` in the kernels): with the fold ring its wave's entry and its frame within
 // the job; with the sample buffer its frame of the launch.
+template <int RING>
 __device__ __forceinline__ uint32_t sample_ref(const WaveJobs& J, uint32_t f0, uint32_t fj) {
-    return kargs()->ring_mode ? (J.cur() << 16) | fj : f0 + fj;
+    return fold_ring<RING>() ? (J.cur() << 16) | fj : f0 + fj;
 }
 
 // cost: the sample's queries (its tile's cost for the next launch's deal order, cost-ordered dealing)
+template <int RING>
 __device__ __forceinline__ void ring_store(const WaveJobs& J, uint32_t pix, uint32_t ref, const f3 c, uint32_t cost) {
     const KPtr K = kargs();
-    if (!K->ring_mode) {  // sample buffer: the colour at its frame of the launch, folded by k_accumulate
+    if (!fold_ring<RING>()) {  // sample buffer: the colour at its frame of the launch, folded by k_accumulate
         const uint32_t npix = K->tiles_w * K->tiles_h * 64u;  // tile-padded pixels of a frame (< 2^32)
         float* o = K->samples + ((unsigned long long)ref * npix + pix) * 3u;  // one 32 x 32 + 64 multiply-add
 #if defined(HRT_STAMPS) && defined(HRT_DIAG_NOSTORE)  // (timing-only diagnostic build: wrong images)
@@ -1949,10 +1974,10 @@ __device__ __forceinline__ bool idle_spin(const WaveJobs& J, uint32_t lane) {
 
 // One job of the wave is complete (every sample stored): set its bit in the tile's fold word and, in the same
 // atomic, try the fold lock; the wave that gets it folds (fold_session), else the holder folds this job too.
-template <uint32_t U>
+template <int RING, uint32_t U>
 __device__ __forceinline__ void job_complete(uint32_t tile, uint32_t c, uint32_t slot, uint32_t lane) {
     const KPtr K = kargs();
-    if (!K->ring_mode) return;  // sample buffer: k_accumulate folds after the launch
+    if (!fold_ring<RING>()) return;  // sample buffer: k_accumulate folds after the launch
     if (lane == 0) __hip_atomic_store(K->job_slot + tile * K->nchunks + c, slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sample stores (and the slot) have reached memory
     unsigned long long old = 0;
@@ -1969,10 +1994,11 @@ __device__ __forceinline__ void job_close(const WaveJobs& J, uint32_t /*lane*/) 
 }
 
 // The waiting current job polls the free queue for its slot (job j >= ring_jobs takes return j - ring_jobs).
+template <int RING>
 __device__ __forceinline__ bool slot_poll(const WaveJobs& J, uint32_t flags, uint32_t lane) {
     if (flags & WJ_SLOTTED) return true;
     const KPtr K = kargs();
-    if (!K->ring_mode) {  // sample buffer: no slot to wait for
+    if (!fold_ring<RING>()) {  // sample buffer: no slot to wait for
         J.set(WJ_FLAGS, flags | WJ_SLOTTED);
         return true;
     }
@@ -2028,12 +2054,12 @@ __device__ __forceinline__ uint32_t queue_take_lane0(const WaveJobs& J, const KP
 // false: nothing to deal now (queue drained -> `drained`; every entry still in flight; slot still folding).
 // TAIL: the sample buffer's quarter jobs at the end of the launch (renderer.cpp tail_from; k_trace_split only:
 // the decode cost the walk kernels of the other programs 2-6 spilled VGPRs).
-template <bool TAIL = false>
+template <int RING, bool TAIL = false>
 __device__ __forceinline__ bool job_acquire(const WaveJobs& J, uint32_t lane, bool& drained, uint32_t& job_tile,
                                             uint32_t& job_f0, uint32_t& job_nf) {
     const KPtr K = kargs();
     uint32_t flags = J.get(WJ_FLAGS);
-    if (!K->ring_mode) {  // sample buffer: no entries, no slots
+    if (!fold_ring<RING>()) {  // sample buffer: no entries, no slots
         uint32_t j = 0;
         if (lane == 0) j = queue_take_lane0(J, K);
         j = uniform(__shfl(j, 0));
@@ -2087,7 +2113,7 @@ __device__ __forceinline__ bool job_acquire(const WaveJobs& J, uint32_t lane, bo
         flags = (flags & ~((3u << WJ_CUR_SHIFT) | WJ_SLOTTED)) | (1u << e) | (e << WJ_CUR_SHIFT) | WJ_WAITING;
         J.set(WJ_FLAGS, flags);
     }
-    if (!slot_poll(J, flags, lane)) return false;
+    if (!slot_poll<RING>(J, flags, lane)) return false;
     const uint32_t cur = (flags >> WJ_CUR_SHIFT) & 3u;
     J.set(WJ_FLAGS, (flags & ~(WJ_WAITING | WJ_SLOTTED)) | WJ_DEALING);
     job_tile = J.get(WJ_TILE + cur);
@@ -2097,8 +2123,9 @@ __device__ __forceinline__ bool job_acquire(const WaveJobs& J, uint32_t lane, bo
 }
 
 // Samples just dealt from the current job (lanes that took one).
+template <int RING>
 __device__ __forceinline__ void job_dealt(const WaveJobs& J, uint32_t n) {
-    if (n == 0u || !kargs()->ring_mode) return;
+    if (!fold_ring<RING>() || n == 0u) return;
     J.set(WJ_IDLE, 0u);
     const uint32_t i = WJ_LIVE + ((J.get(WJ_FLAGS) >> WJ_CUR_SHIFT) & 3u);
     J.set(i, J.get(i) + n);
@@ -2107,9 +2134,9 @@ __device__ __forceinline__ void job_dealt(const WaveJobs& J, uint32_t n) {
 // End of a round: lanes whose sample finished (`fin`, colour stored) are counted off their jobs (the busy entry
 // whose tile and frames hold the sample); jobs neither current nor with anything in flight complete, and a job
 // that completes its tile folds it.
-template <uint32_t U = 2>
+template <int RING, uint32_t U = 2>
 __device__ __forceinline__ void job_account(const WaveJobs& J, bool fin, uint32_t ref, uint32_t lane) {
-    if (!kargs()->ring_mode) return;  // sample buffer: nothing to track
+    if (!fold_ring<RING>()) return;  // sample buffer: nothing to track
     const unsigned long long any = __ballot(fin);
     if (any != 0ull) {
         const uint32_t idx = ref >> 16;
@@ -2121,7 +2148,7 @@ __device__ __forceinline__ void job_account(const WaveJobs& J, bool fin, uint32_
     }
     {
         const uint32_t flags = J.get(WJ_FLAGS);
-        if (flags & WJ_WAITING) (void)slot_poll(J, flags, lane);  // every round, not only when lanes are free
+        if (flags & WJ_WAITING) (void)slot_poll<RING>(J, flags, lane);  // every round, not only when lanes are free
     }
 #pragma nounroll
     for (uint32_t e = 0; e < WJ_NE; e++) {
@@ -2132,7 +2159,7 @@ __device__ __forceinline__ void job_account(const WaveJobs& J, bool fin, uint32_
 #ifdef HRT_RINGSTAT
             const unsigned long long t0 = __builtin_readcyclecounter();
 #endif
-            job_complete<U>(J.get(WJ_TILE + e), J.get(WJ_F0 + e) >> kargs()->jf_log2, J.get(WJ_SLOT + e), lane);
+            job_complete<RING, U>(J.get(WJ_TILE + e), J.get(WJ_F0 + e) >> kargs()->jf_log2, J.get(WJ_SLOT + e), lane);
 #ifdef HRT_RINGSTAT
             RINGSTAT_ADD(J, 2, 1);
             RINGSTAT_ADD(J, 3, (__builtin_readcyclecounter() - t0) >> 4);
@@ -2321,7 +2348,7 @@ struct BlockQueue {
 };
 
 // Free lanes (!have) take the next samples; sets drained once the job queue is empty.
-template <int MODE>
+template <int MODE, bool RING>
 __device__ __forceinline__ void refill_block(const KParams& P, BlockQueue& B, const WaveJobs& J, bool& drained, uint32_t lane,
                                              unsigned long long below, bool& have, Ray& ray, f3& att,
                                              float& sky_t, uint32_t& s, uint32_t& bounce, uint32_t& pix,
@@ -2333,7 +2360,7 @@ __device__ __forceinline__ void refill_block(const KParams& P, BlockQueue& B, co
             if (J.dealing()) {
                 B.blk_f++;
             } else {
-                if (!job_acquire(J, lane, drained, B.job_tile, B.job_f0, B.job_nf)) break;
+                if (!job_acquire<RING>(J, lane, drained, B.job_tile, B.job_f0, B.job_nf)) break;
                 B.blk_f = 0;
 #ifdef HRT_STAMPS
                 {
@@ -2375,7 +2402,7 @@ __device__ __forceinline__ void refill_block(const KParams& P, BlockQueue& B, co
                 ray.o = mk(ox, oy, oz);
                 ray.d = mk(dx, dy, dz);
                 s = ss;
-                fl = sample_ref(J, B.job_f0, B.blk_f);
+                fl = sample_ref<RING>(J, B.job_f0, B.blk_f);
                 pix = B.job_tile * 64u + (uint32_t)src;
                 sky_t = ray.d.y * 0.5f + 0.5f;
                 att = mk(1.0f, 1.0f, 1.0f);
@@ -2384,7 +2411,7 @@ __device__ __forceinline__ void refill_block(const KParams& P, BlockQueue& B, co
                 took = true;
             }
         }
-        job_dealt(J, (uint32_t)__popcll(__ballot(took)));
+        job_dealt<RING>(J, (uint32_t)__popcll(__ballot(took)));
         B.blk_next += min((uint32_t)__popcll(m), avail);
         if (B.blk_next == 64u && B.blk_f + 1u >= B.job_nf) job_close(J, lane);
         m = __ballot(need);
@@ -2670,11 +2697,9 @@ struct BlockState {
 #ifndef HRT_UGUARD_KTRACE
 #define HRT_UGUARD_KTRACE 1  // (k_trace's sphere program: the exact sequences' guards as wave-uniform branches)
 #endif
-template <int MODE, int SCAN, bool TSAH = false>
-// 6 waves per SIMD: the register budget is 80 VGPRs (84 unconstrained = 5 waves; measured +8% on C3)
-// (the mixed program's deferred scan holds 32 KB of LDS per workgroup: 5 waves/SIMD whatever the VGPRs)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
-    TSAH || (MODE == MODE_MIXED && SCAN == SCAN_DEFER) ? 5 : 6))) void k_trace(const KParams P) {
+// (the body of k_trace and k_ring: the two fold modes, below)
+template <int MODE, int SCAN, bool TSAH, bool RING>
+__device__ __forceinline__ void trace_queue(const KParams& P) {
     const uint32_t lane = threadIdx.x & 63u;
     const LaneLists lists = lane_lists<MODE, SCAN>();
     void* const lds_list = lists.sphere;
@@ -2714,7 +2739,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
         constexpr bool BLOCK_REFILL = MODE == MODE_SPHERE && SCAN == SCAN_SIMPLE;
         bool need = !have && !drained;
         if constexpr (BLOCK_REFILL) {
-            refill_block<MODE>(P, BQ, J, drained, lane, below, have, ray, att, sky_t, s, bounce, pix, fl);
+            refill_block<MODE, RING>(P, BQ, J, drained, lane, below, have, ray, att, sky_t, s, bounce, pix, fl);
             need = false;
         }
         unsigned long long m = __ballot(need);
@@ -2722,7 +2747,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             if (!J.dealing()) {
                 // tile-major job order: one tile's frame chunks are handed out together and run on
                 // neighbouring waves at once, so an expensive tile finishes early instead of trailing
-                if (!job_acquire(J, lane, drained, job_tile, job_f0, job_nf)) break;
+                if (!job_acquire<RING>(J, lane, drained, job_tile, job_f0, job_nf)) break;
                 job_total = 64u * job_nf;
                 job_next = 0;
             }
@@ -2732,7 +2757,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             if (need && rank < avail) {
                 const uint32_t sid = job_next + rank;
                 const uint32_t l = sid & 63u;
-                fl = sample_ref(J, job_f0, sid >> 6);
+                fl = sample_ref<RING>(J, job_f0, sid >> 6);
                 pix = job_tile * 64u + l;
                 // (the SAH-walk kernels read the tile map, row map and time through kargs() here: SGPRs)
 #define HRT_KF(f) (TSAH ? kargs()->f : P.f)
@@ -2750,7 +2775,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
                     took_ok = true;
                 }
             }
-            job_dealt(J, (uint32_t)__popcll(__ballot(took_ok)));
+            job_dealt<RING>(J, (uint32_t)__popcll(__ballot(took_ok)));
             const uint32_t took = min((uint32_t)__popcll(m), avail);
             job_next += took;
             if (job_next == job_total) job_close(J, lane);
@@ -2798,7 +2823,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             const float u = 1.0f - sky_t;
             const f3 sky = mk(0.54f * u + 0.54f * sky_t, 0.86f * u + 0.7f * sky_t, 0.92f * u + 0.98f * sky_t);
             const f3 c = att * sky;
-            ring_store(J, pix, fl, c, bounce + 1u);
+            ring_store<RING>(J, pix, fl, c, bounce + 1u);
             have = false;
             fin = true;
         }
@@ -2807,7 +2832,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
         wrec.round((uint32_t)__popcll(__ballot(fin)), BQ.took_job != 0u);
         BQ.took_job = 0u;
 #endif
-        job_account(J, fin, fl, lane);
+        job_account<RING>(J, fin, fl, lane);
     }
 #ifdef HRT_STAMPS
     wrec.finish(P, lane, BQ.njobs, BQ.last_job, BQ.max_job);
@@ -2845,6 +2870,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     }
     if (lane == 0) flush_counts(sums);
 }
+// One kernel per fold mode (fold_ring): k_trace with the sample buffer, k_ring with the fold ring. A name of its own, not a
+// fifth template argument, keeps k_trace's symbol what rt_stats.kernel says (bench.py matches it against rocprofv3
+// summaries, tests/test_gpu_kernels.py against the code object); rt_stats.kernel names k_trace in both modes and
+// rt_stats.fold_ring the mode.
+// 6 waves per SIMD: the register budget is 80 VGPRs (84 unconstrained = 5 waves; measured +8% on C3)
+// (the mixed program's deferred scan holds 32 KB of LDS per workgroup: 5 waves/SIMD whatever the VGPRs)
+// (HRT_KTRACE_PIN 1, A/B builds: the target as the maximum too — with the fold mode compiled in the linear scans need
+// 60 VGPRs and run 8 waves per SIMD where the runtime-switched kernel ran 6)
+#ifndef HRT_KTRACE_PIN
+#define HRT_KTRACE_PIN 0
+#endif
+#if HRT_KTRACE_PIN
+#define HRT_KTRACE_WAVES(w) amdgpu_waves_per_eu(w, w)
+#else
+#define HRT_KTRACE_WAVES(w) amdgpu_waves_per_eu(w)
+#endif
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) __attribute__((HRT_KTRACE_WAVES(
+    (TSAH || (MODE == MODE_MIXED && SCAN == SCAN_DEFER) ? 5 : 6)))) void k_trace(const KParams P) {
+    trace_queue<MODE, SCAN, TSAH, false>(P);
+}
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) __attribute__((HRT_KTRACE_WAVES(
+    (TSAH || (MODE == MODE_MIXED && SCAN == SCAN_DEFER) ? 5 : 6)))) void k_ring(const KParams P) {
+    trace_queue<MODE, SCAN, TSAH, true>(P);
+}
 
 
 // Frame-block refill with the block in LDS (k_trace_split_tris; k_trace_split has the same code inline, which
@@ -2859,7 +2910,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 // five PCG steps. (Two float4 per lane before round 4: the bytes saved hold the whole heap top.)
 
 
-template <int MODE, bool STEAL, bool SEED>
+template <int MODE, bool STEAL, bool SEED, bool RING>
 __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B, const WaveJobs& J, float* blk,
                                                  uint32_t* rows, uint32_t* okw, bool& drained,
                                                  uint32_t lane, unsigned long long below, bool& have,
@@ -2887,7 +2938,7 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
                 } else {
                     // (the tail: once this wave dealt a tail part, a new one only for CLAIM_FREE free lanes, as stealing)
                     if (TAIL_CLAIM && (J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull) break;
-                    if (!job_acquire<true>(J, lane, drained, B.job_tile, B.job_f0, B.job_nf)) break;
+                    if (!job_acquire<RING, true>(J, lane, drained, B.job_tile, B.job_f0, B.job_nf)) break;
                     B.blk_f = 0;
                 }
             }
@@ -2950,7 +3001,7 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
                     for (int k = 0; k < 5; k++) st = pcg_next(st);  // primary_ray's five draws (r1, r2, q1, q2, rr)
                     s = st;
                 }
-                fl = sample_ref(J, B.job_f0, B.blk_f);
+                fl = sample_ref<RING>(J, B.job_f0, B.blk_f);
                 pix = B.job_tile * 64u + src;
                 sky_t = ray.d.y * 0.5f + 0.5f;
                 att = mk(1.0f, 1.0f, 1.0f);
@@ -2960,7 +3011,7 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
                 took = true;
             }
         }
-        job_dealt(J, (uint32_t)__popcll(__ballot(took)));
+        job_dealt<RING>(J, (uint32_t)__popcll(__ballot(took)));
         B.blk_next += min((uint32_t)__popcll(m), avail);
         if (B.blk_next == 64u && B.blk_f + 1u >= B.job_nf) job_close(J, lane);
         m = __ballot(need);
@@ -3021,7 +3072,20 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
 // made (packet_walk: all 64 lanes, wave-uniform traversal), and the block entry carries the resolved first hit — the
 // hit point in place of the origin and the winner's slot — so a lane that takes the sample shades it at once (qs 4)
 // instead of walking its primary ray beside the wave's incoherent secondary walks. Same bits and query counts.
-template <bool LNODES, bool STEAL, bool COUNT, bool PACKET>
+// RING: the fold mode (fold_ring; k_ring_split below; never with STEAL; the packet kernels test it at run time: FOLD_DYN).
+// STACK16 (LNODES without PACKET): the walk stack's entries are 16 bits. An LNODES child word is a node index < LNODE_CAP
+// or LEAF | first << 4 | count with first < 2048 (renderer.cpp's gate), 15 bits and the leaf bit; the LDS copy of the
+// nodes holds them sign-extended from bit 15 (leaf bit kept in bit 31), so the push stores a word's low half and the
+// pop's sign-extending 16-bit read returns the word it was: no instruction added to either. The workgroup's LDS drops
+// by 4 KB, to 8 x 18.5 KB per CU.
+// 8 waves per SIMD (split_waves) for the sample-buffer kernels without counting, stealing and packets: with the ring
+// compiled out they fit 64 VGPRs without scratch. The others keep 7 (12 to 52 B of scratch at 64 VGPRs).
+#ifndef HRT_STACK16
+#define HRT_STACK16 1
+#endif
+#ifndef HRT_SPLIT_WAVES8
+#define HRT_SPLIT_WAVES8 1
+#endif
 #ifndef HRT_PACKET_WAVES
 #define HRT_PACKET_WAVES 7
 #endif
@@ -3031,9 +3095,18 @@ template <bool LNODES, bool STEAL, bool COUNT, bool PACKET>
 #ifndef HRT_SPLIT_WAVES
 #define HRT_SPLIT_WAVES 7
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (STEAL ? HRT_PACKET_STEAL_WAVES : HRT_PACKET_WAVES) : HRT_SPLIT_WAVES))) void k_trace_split(const KParams P) {
+constexpr bool split_stack16(bool lnodes, bool packet) { return HRT_STACK16 && lnodes && !packet; }
+// (8 only where the workgroup's LDS leaves room for an eighth, the 16-bit stack, and with the fold mode compiled in)
+constexpr int split_waves(bool lnodes, bool steal, bool count, bool packet, bool ring) {
+    if (packet) return steal ? HRT_PACKET_STEAL_WAVES : HRT_PACKET_WAVES;
+    return HRT_SPLIT_WAVES8 && HRT_FOLD_TEMPLATE && split_stack16(lnodes, packet) && !steal && !count && !ring ? 8 : HRT_SPLIT_WAVES;
+}
+template <bool LNODES, bool STEAL, bool COUNT, bool PACKET, bool RING>
+__device__ __forceinline__ void trace_split(const KParams& P) {
     static_assert(!PACKET || LNODES, "the packet walk reads the LDS nodes and keeps its stack in one VGPR (depth <= 8)");
     constexpr int MODE = MODE_SPHERE;
+    constexpr int FM = PACKET ? FOLD_DYN : (int)RING;  // (the packet kernels: one instantiation for both fold modes)
+    static_assert(!(PACKET && RING) && !(STEAL && RING), "no such instantiation: launch_trace_split");
     constexpr int SPLIT_STACK = LNODES ? (int)LNODE_DEPTH : 14;
 #ifndef HRT_SHADE_BY_CODE
 #define HRT_SHADE_BY_CODE 1
@@ -3041,7 +3114,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     // (the packet kernels' block entries carry the winner's slot: they shade from the slot table)
     constexpr bool SHADE_BY_CODE = HRT_SHADE_BY_CODE && !PACKET;
     const uint32_t lane = threadIdx.x & 63u;
-    __shared__ uint32_t bvh_stack[SPLIT_STACK * 256];
+    constexpr bool STACK16 = split_stack16(LNODES, PACKET);
+    static_assert(!STACK16 || (LNODE_CAP <= 0x8000u && (LNODE_CAP + 1u) * BVH_MAX_LEAF <= 2048u),
+                  "a 16-bit stack entry holds a node index or first << 4 | count in 15 bits");
+    using StackWord = std::conditional_t<STACK16, int16_t, uint32_t>;
+    __shared__ StackWord bvh_stack[SPLIT_STACK * 256];
     __shared__ uint4 lnodes[LNODES ? 2 * LNODE_CAP : 1];
 #ifndef HRT_LLARGE_LDS
 #define HRT_LLARGE_LDS 1
@@ -3051,7 +3128,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     __shared__ float4 lgeo[LLDS ? LLARGE_CAP : 1];  // the large list's spheres: (cx, cy, cz, r*r), in list order
     if constexpr (LNODES) {
         const uint32_t nn = 2u * min(P.bvh_nnodes, LNODE_CAP);  // renderer.cpp gates LNODES on the same cap
-        for (uint32_t i = threadIdx.x; i < nn; i += 256u) lnodes[i] = P.bvh_hnodes[i];
+        for (uint32_t i = threadIdx.x; i < nn; i += 256u) {
+            uint4 c = P.bvh_hnodes[i];
+            if constexpr (STACK16) c.w = (uint32_t)(int32_t)(int16_t)(c.w | (c.w >> 16));  // (leaf bit to bit 15, sign-extended)
+            lnodes[i] = c;
+        }
         if constexpr (LLDS) {
             if (threadIdx.x < min(P.nlarge, LLARGE_CAP)) {  // renderer.cpp gates LNODES on nlarge <= LLARGE_CAP
                 lgeo[threadIdx.x] = P.sph_geo[P.large_slots[threadIdx.x]];
@@ -3060,10 +3141,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
         __syncthreads();
     }
     __shared__ float4 blk[2 * 256];  // the wave's frame block: (o.xyz, d.x), (d.yz, state bits, ok) per lane
-    uint32_t* const stack = bvh_stack + threadIdx.x;
     Tally tally;
     uint32_t queries = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
     // (one kernarg word: the suspend threshold in bits 0..7, the descent hold in bits 8..15 — renderer.cpp)
     const uint32_t suspend_below = P.suspend_below & 0xFFu, hold = P.suspend_below >> 8;
 
@@ -3081,8 +3160,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     // it, instead of each freed lane computing its own with a few lanes active.
     uint32_t job_tile = 0, job_f0 = 0, job_nf = 0, blk_f = 0, blk_next = 64;  // wave-uniform
     __shared__ uint32_t wjobs[4 * WJ_WORDS];
-    const WaveJobs J = wave_jobs(wjobs);
-    if (P.fold_prev != nullptr) fold_prev_tiles(P, lane);
+    // (the fold ring's launches fold nothing of the launch before: renderer.cpp's fold_next needs the sample buffer)
+    // (the wave's words, the stack pointer and the lane mask after the fold, whose eight frames in flight take the
+    // register budget: nothing of the walk held through it; the packet kernels keep their order, their allocation)
+    const WaveJobs Jp = PACKET ? wave_jobs(wjobs) : WaveJobs{nullptr};
+    StackWord* const stack_p = PACKET ? bvh_stack + threadIdx.x : nullptr;
+    if (FM != 1 && P.fold_prev != nullptr) fold_prev_tiles(P, lane);
+    const WaveJobs J = PACKET ? Jp : wave_jobs(wjobs);
+    StackWord* const stack = PACKET ? stack_p : bvh_stack + threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
     HRT_PHASE_DECL;
 #ifdef HRT_STAMPS
     WaveRecord wrec;
@@ -3111,7 +3197,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
                         // (the tail: once this wave dealt a tail part, a new one only for CLAIM_FREE free lanes, as stealing)
                         if (TAIL_CLAIM && (J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull)
                             break;
-                        if (!job_acquire<true>(J, lane, drained, job_tile, job_f0, job_nf)) break;
+                        if (!job_acquire<FM, true>(J, lane, drained, job_tile, job_f0, job_nf)) break;
                         blk_f = 0;
                     }
                 }
@@ -3198,7 +3284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
                     ray.o = mk(ox, oy, oz);  // (PACKET, resolved hit: the hit point)
                     ray.d = mk(dx, dy, dz);
                     s = ss;
-                    fl = sample_ref(J, job_f0, blk_f);
+                    fl = sample_ref<FM>(J, job_f0, blk_f);
                     pix = job_tile * 64u + (uint32_t)src;
                     sky_t = ray.d.y * 0.5f + 0.5f;
                     att = mk(1.0f, 1.0f, 1.0f);
@@ -3214,7 +3300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
                     took = true;
                 }
             }
-            job_dealt(J, (uint32_t)__popcll(__ballot(took)));
+            job_dealt<FM>(J, (uint32_t)__popcll(__ballot(took)));
             blk_next += min((uint32_t)__popcll(m), avail);
             if (blk_next == 64u && blk_f + 1u >= job_nf) job_close(J, lane);
             m = __ballot(need);
@@ -3301,13 +3387,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
                 const float u = 1.0f - sky_t;
                 const f3 sky = mk(0.54f * u + 0.54f * sky_t, 0.86f * u + 0.7f * sky_t, 0.92f * u + 0.98f * sky_t);
                 const f3 c = att * sky;
-                ring_store(J, pix, fl, c, bounce + 1u);
+                ring_store<FM>(J, pix, fl, c, bounce + 1u);
                 have = false;
                 fin = true;
             }
             qs = 0u;
         }
-        job_account<1>(J, fin, fl, lane);
+        job_account<FM, 1>(J, fin, fl, lane);
         HRT_PHASE(3);
     }
 #ifdef HRT_STAMPS
@@ -3339,6 +3425,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PACKET ? (S
     }
     if (lane == 0) flush_counts(sums);
 }
+// (one kernel per fold mode, as k_trace / k_ring: k_trace_split with the sample buffer, k_ring_split with the fold ring)
+template <bool LNODES, bool STEAL, bool COUNT, bool PACKET>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(split_waves(LNODES, STEAL, COUNT, PACKET, false)))) void
+k_trace_split(const KParams P) {
+    trace_split<LNODES, STEAL, COUNT, PACKET, false>(P);
+}
+template <bool LNODES, bool COUNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(split_waves(LNODES, false, COUNT, false, true)))) void
+k_ring_split(const KParams P) {
+    trace_split<LNODES, false, COUNT, false, true>(P);
+}
 
 // Sample queue with suspendable walks for the triangle and mixed programs (reference heap walk; the
 // sphere part of the mixed program is `SCAN`: the linear scan, simple or deferred, or the culling BVH
@@ -3367,9 +3464,8 @@ constexpr uint32_t heap_top_n(int hl, int scan) { return hl == 0 ? 0u : hl == 1 
 #ifndef HRT_UGUARD_TRIS
 #define HRT_UGUARD_TRIS 1  // (the mixed kernels' sphere hit record with the linear scan (C4): its normal division's guard as
 #endif                     //  a wave-uniform branch, +0.3 %; with the culling BVH (C5) -0.1 %, so not there)
-template <int MODE, int SCAN, int HL, bool STEAL>
-__global__ __launch_bounds__(heap_wg(HL)) __attribute__((amdgpu_waves_per_eu(SCAN == SCAN_DEFER ? 5 : 6))) void
-k_trace_split_tris(const KParams P) {
+template <int MODE, int SCAN, int HL, bool STEAL, bool RING>
+__device__ __forceinline__ void trace_split_tris(const KParams& P) {
     static_assert(MODE != MODE_SPHERE, "k_trace_split covers the sphere program");
     constexpr uint32_t WGT = heap_wg(HL), HT = heap_top_n(HL, SCAN);
     const uint32_t lane = threadIdx.x & 63u;
@@ -3424,7 +3520,7 @@ k_trace_split_tris(const KParams P) {
     wrec.begin();
 #endif
     while (true) {
-        refill_block_lds<MODE, STEAL, SEED>(P, B, J, blk, blk_rows, blk_ok, drained, lane, below, have, qs, ray, att, sky_t, s,
+        refill_block_lds<MODE, STEAL, SEED, RING>(P, B, J, blk, blk_rows, blk_ok, drained, lane, below, have, qs, ray, att, sky_t, s,
                                             bounce, pix, fl);
 #ifdef HRT_STAMPS
         wrec.drain(drained);
@@ -3500,13 +3596,13 @@ k_trace_split_tris(const KParams P) {
                 const float u = 1.0f - sky_t;
                 const f3 sky = mk(0.54f * u + 0.54f * sky_t, 0.86f * u + 0.7f * sky_t, 0.92f * u + 0.98f * sky_t);
                 const f3 c = att * sky;
-                ring_store(J, pix, fl, c, bounce + 1u);
+                ring_store<RING>(J, pix, fl, c, bounce + 1u);
                 have = false;
                 fin = true;
             }
             qs = 0u;
         }
-        job_account<SCAN == SCAN_BVH ? 1 : 2>(J, fin, fl, lane);
+        job_account<RING, SCAN == SCAN_BVH ? 1 : 2>(J, fin, fl, lane);
         HRT_PHASE(3);
     }
 #ifdef HRT_STAMPS
@@ -3538,6 +3634,17 @@ k_trace_split_tris(const KParams P) {
         for (int off = 32; off > 0; off >>= 1) sums[c] += __shfl_xor(sums[c], off);
     }
     if (lane == 0) flush_counts(sums);
+}
+// (one kernel per fold mode, as k_trace / k_ring; the fold ring never with stealing)
+template <int MODE, int SCAN, int HL, bool STEAL>
+__global__ __launch_bounds__(heap_wg(HL)) __attribute__((amdgpu_waves_per_eu(SCAN == SCAN_DEFER ? 5 : 6))) void
+k_trace_split_tris(const KParams P) {
+    trace_split_tris<MODE, SCAN, HL, STEAL, false>(P);
+}
+template <int MODE, int SCAN, int HL>
+__global__ __launch_bounds__(heap_wg(HL)) __attribute__((amdgpu_waves_per_eu(SCAN == SCAN_DEFER ? 5 : 6))) void
+k_ring_split_tris(const KParams P) {
+    trace_split_tris<MODE, SCAN, HL, false, true>(P);
 }
 
 // Sample buffer (ring_mode 0): folds P.nframes sample colours per pixel into the image, in frame order, with the
@@ -4148,8 +4255,10 @@ static hipError_t launch_persistent(K kernel, const KParams& P, hipStream_t stre
 template <int MODE, int SCAN, int HL>
 static hipError_t launch_split_tris_hl(const KParams& P, hipStream_t stream) {
     const char* base = "k_trace_split_tris";
-    return P.steal ? launch_persistent(k_trace_split_tris<MODE, SCAN, HL, true>, P, stream, kname_iiib(base, MODE, SCAN, HL, 1), heap_wg(HL))
-                   : launch_persistent(k_trace_split_tris<MODE, SCAN, HL, false>, P, stream, kname_iiib(base, MODE, SCAN, HL, 0), heap_wg(HL));
+    // (the fold ring's kernel is displayed under the sample buffer's name: rt_stats.fold_ring reports the mode)
+    if (P.steal) return launch_persistent(k_trace_split_tris<MODE, SCAN, HL, true>, P, stream, kname_iiib(base, MODE, SCAN, HL, 1), heap_wg(HL));
+    return P.ring_mode ? launch_persistent(k_ring_split_tris<MODE, SCAN, HL>, P, stream, kname_iiib(base, MODE, SCAN, HL, 0), heap_wg(HL))
+                       : launch_persistent(k_trace_split_tris<MODE, SCAN, HL, false>, P, stream, kname_iiib(base, MODE, SCAN, HL, 0), heap_wg(HL));
 }
 template <int MODE, int SCAN>
 static hipError_t launch_split_tris(const KParams& P, hipStream_t stream) {
@@ -4168,6 +4277,14 @@ static hipError_t launch_split_tris(const KParams& P, hipStream_t stream) {
 // suspendable-walk kernels (renderer.cpp sets suspend_below >= 1 for them; 1 = a wave never leaves a walk early);
 // k_trace is instantiated only for what has no split kernel: the sphere program's linear scans and the opt-in SAH
 // triangle walk (tri_bvh = 1).
+// k_trace<MODE, SCAN, TSAH> or, with the fold ring, k_ring<MODE, SCAN, TSAH> (displayed as k_trace: rt_stats.fold_ring)
+template <int MODE, int SCAN, bool TSAH>
+static hipError_t launch_k_trace(const KParams& P, hipStream_t stream) {
+    const char* name = kname("k_trace", MODE, SCAN, (int)TSAH);
+    return P.ring_mode ? launch_persistent(k_ring<MODE, SCAN, TSAH>, P, stream, name)
+                       : launch_persistent(k_trace<MODE, SCAN, TSAH>, P, stream, name);
+}
+
 template <int MODE, bool TSAH>
 static hipError_t launch_trace_mode(int variant, const KParams& P, hipStream_t stream) {
     if constexpr (MODE != MODE_SPHERE && !TSAH) {
@@ -4184,22 +4301,28 @@ static hipError_t launch_trace_mode(int variant, const KParams& P, hipStream_t s
             return launch_split_tris<MODE, SCAN_BVH>(P, stream);
         }
     } else if constexpr (MODE == MODE_TRIS) {
-        return launch_persistent(k_trace<MODE, SCAN_SIMPLE, TSAH>, P, stream, kname("k_trace", MODE, SCAN_SIMPLE, (int)TSAH));
+        return launch_k_trace<MODE, SCAN_SIMPLE, TSAH>(P, stream);
     } else {
-        if (variant == SCAN_SIMPLE) return launch_persistent(k_trace<MODE, SCAN_SIMPLE, TSAH>, P, stream, kname("k_trace", MODE, SCAN_SIMPLE, (int)TSAH));
-        if (variant == SCAN_DEFER) return launch_persistent(k_trace<MODE, SCAN_DEFER, TSAH>, P, stream, kname("k_trace", MODE, SCAN_DEFER, (int)TSAH));
+        if (variant == SCAN_SIMPLE) return launch_k_trace<MODE, SCAN_SIMPLE, TSAH>(P, stream);
+        if (variant == SCAN_DEFER) return launch_k_trace<MODE, SCAN_DEFER, TSAH>(P, stream);
         if constexpr (MODE == MODE_SPHERE) {
             return hipErrorInvalidValue;  // the culling BVH runs in k_trace_split
         } else {
-            return launch_persistent(k_trace<MODE, SCAN_BVH, TSAH>, P, stream, kname("k_trace", MODE, SCAN_BVH, (int)TSAH));
+            return launch_k_trace<MODE, SCAN_BVH, TSAH>(P, stream);
         }
     }
 }
 
-// k_trace_split<LNODES, STEAL, COUNT, PACKET> by P.bvh_lnodes / P.steal / P.packet (PACKET only with LNODES)
+// k_trace_split<LNODES, STEAL, COUNT, PACKET> by P.bvh_lnodes / P.steal / P.packet (PACKET only with LNODES), or with the
+// fold ring k_ring_split<LNODES, COUNT> (never with STEAL: hrt_launch_trace), displayed as k_trace_split<.., false, ..,
+// false>: rt_stats.fold_ring reports the mode.
 template <bool COUNT>
 static hipError_t launch_trace_split(const KParams& P, hipStream_t stream) {
     const char* base = "k_trace_split";
+    if (P.ring_mode && !(P.bvh_lnodes && P.packet)) {  // (the packet kernels test the mode at run time)
+        return P.bvh_lnodes ? launch_persistent(k_ring_split<true, COUNT>, P, stream, kname_bbbb(base, 1, 0, COUNT, 0))
+                            : launch_persistent(k_ring_split<false, COUNT>, P, stream, kname_bbbb(base, 0, 0, COUNT, 0));
+    }
     if (P.bvh_lnodes && P.packet) {
         return P.steal ? launch_persistent(k_trace_split<true, true, COUNT, true>, P, stream, kname_bbbb(base, 1, 1, COUNT, 1))
                        : launch_persistent(k_trace_split<true, false, COUNT, true>, P, stream, kname_bbbb(base, 1, 0, COUNT, 1));
@@ -4217,6 +4340,7 @@ hipError_t hrt_launch_trace(int mode, int variant, const KParams& P, hipStream_t
     // (job_acquire<TAIL>): k_trace_split and k_trace_split_tris (not the opt-in SAH walk's k_trace)
     const bool split_kernel = mode == MODE_SPHERE ? (variant == SCAN_BVH && P.suspend_below > 0u) : !P.tri_bvh;
     if (P.tail_from != 0xFFFFFFFFu && !(split_kernel && !P.steal && !P.ring_mode)) return hipErrorInvalidValue;
+    if (P.steal && P.ring_mode) return hipErrorInvalidValue;  // stealing: the sample buffer only (no such instantiation)
     switch (mode) {
     case MODE_SPHERE:
         if (variant == SCAN_BVH && P.suspend_below > 0u)

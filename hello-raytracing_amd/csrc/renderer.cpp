@@ -145,7 +145,7 @@ uint32_t local_rows_of(uint32_t H, uint32_t row0, uint32_t step, uint32_t block)
     return (uint32_t)((nblocks - 1) * block + std::min<uint64_t>(block, H - last0));
 }
 
-// The descent hold of k_trace_split<LNODES> (rt_kernels.hip bvh_run<.., HOLD>): 0 = off. Not an rt_params field: a
+// The descent hold of k_trace_split<LNODES> (rt_kernels.hip bvh_walk_noovf<.., HOLD>): 0 = off. Not an rt_params field: a
 // product caller has no use for it; hrt_testing.h moves it for the tests and the sweeps.
 constexpr uint32_t DESCENT_HOLD_DEFAULT = 12u;
 
@@ -241,13 +241,8 @@ struct rt_renderer {
     size_t image_floats() const { return (size_t)local_rows() * width * 3u; }
 };
 
-#ifndef HRT_LNODES
-#define HRT_LNODES 1
-#endif
 // heap-top configuration of k_trace_split_tris when rt_params.heap_lds = 0 (rt_kernels.hip heap_top_n)
-#ifndef HRT_HEAP_AUTO
-#define HRT_HEAP_AUTO 3u
-#endif
+constexpr uint32_t HEAP_AUTO = 3u;
 
 namespace {
 
@@ -563,7 +558,7 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     P.bvh_rr_h = std::nextafter(B.root_radius * (1.0f + 0x1p-9f), INFINITY);
     P.bvh_nnodes = (uint32_t)B.nodes.size();
     // (the large list in LDS too: LLARGE_CAP; the leaf spheres: a leaf word in a 16-bit walk-stack entry)
-    P.bvh_lnodes = (HRT_LNODES && B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH &&
+    P.bvh_lnodes = (B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH &&
                     B.large.size() <= hrt_dev::LLARGE_CAP && B.slot.size() <= hrt_dev::LNODE_LEAF_SPHERES) ? 1u : 0u;
     // (0 auto = off: the packet walk measured -8 % on C3)
     P.packet = (P.bvh_lnodes && r->params.packet == 2u) ? 1u : 0u;
@@ -643,7 +638,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         if (r->mode != RT_MODE_SPHERE &&
             (r->mode == RT_MODE_TRIS || variant != hrt_dev::SCAN_BVH || r->bvh_host.depth <= 8u) && r->params.heap_lds != 1u &&
             r->bvh_n <= (1u << 24))
-            P.tri_small = HRT_HEAP_AUTO;
+            P.tri_small = HEAP_AUTO;
         if (variant == hrt_dev::SCAN_DEFER && r->mode == RT_MODE_MIXED && P.tri_small > 1u) P.tri_small = 1u;
         // job_frames 0 = per kernel: 32 for the suspendable walks (C3 +0.7 %, C4 +1.5 % over 16), 16 for k_trace's
         // cheap sphere scans (C2: 32 costs 3 %); a power of two (the ring's slot layout)
@@ -775,10 +770,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
             P.jf_log2--;
         }
         P.queue = r->counter.ptr + 15u;
-        // the sample buffer's jobs from one counter per XCD (HRT_NQ 0: the single counter)
-#ifndef HRT_NQ
-#define HRT_NQ 1
-#endif
+        // the sample buffer's jobs from one counter per XCD
         constexpr size_t QWORDS = (size_t)hrt_dev::NQ * hrt_dev::QSTRIDE;
         P.queues = nullptr;
         if (!P.ring_mode) {  // (+ the fold counter, below)
@@ -791,10 +783,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         // the automatic colour budget (it doubles the colour memory: C3 17.5 GB). C3 38.38 -> 38.76-38.83 Grays/s with 1 in
         // 32 / 64 / 128 waves folding, 38.62-38.65 with 1 in 16, 38.30-38.44 with 1 in 1 or 4; C5 +0.2 %
         // (profiles/r06/fold_next/).
-#ifndef HRT_FOLD_WAVE_MOD
-#define HRT_FOLD_WAVE_MOD 64
-#endif
-        constexpr uint32_t FOLD_WAVE_MOD = HRT_FOLD_WAVE_MOD;
+        constexpr uint32_t FOLD_WAVE_MOD = 64;
         bool fold_next = !P.ring_mode && split && count > chunk &&
                          (r->params.fold == RT_FOLD_NEXT || (r->params.fold == RT_FOLD_AUTO && r->params.queue_budget_mb == 0u));
         if (fold_next) {
@@ -865,7 +854,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
             r->ring_nchunks = P.nchunks;
             HIP_TRY(hipMemsetAsync(P.queue, 0, sizeof(unsigned long long), r->stream));
             // (not with stealing: its launches are short, and the per-XCD fetch spilled SGPRs in the stealing kernels)
-            P.queues = HRT_NQ && !P.ring_mode && !P.steal ? r->queues.ptr : nullptr;
+            P.queues = !P.ring_mode && !P.steal ? r->queues.ptr : nullptr;
             if (P.queues) HIP_TRY(hipMemsetAsync(P.queues, 0, QWORDS * sizeof(unsigned long long), r->stream));
             if (P.steal) HIP_TRY(hipMemsetAsync(P.steal_slots, 0, P.steal_cap * sizeof(unsigned long long), r->stream));
             if (P.ring_mode) HIP_TRY(hipMemsetAsync(r->ring_ctl.ptr, 0, zero_words * sizeof(uint32_t), r->stream));

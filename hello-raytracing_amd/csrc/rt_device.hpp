@@ -70,10 +70,7 @@ constexpr int SCAN_SIMPLE = 1;  // one slot per iteration, exact sqrt/div whenev
 constexpr int SCAN_DEFER = 3;   // slot pairs, packed math, candidate list in LDS, exact resolution after
 constexpr int SCAN_BVH = 4;     // conservative BVH culling + exact tests, (t, slot) lexicographic min
 constexpr uint32_t BVH_LEAF_BIT = 0x80000000u;
-#ifndef HRT_BVH_STACK
-#define HRT_BVH_STACK 24
-#endif
-constexpr int BVH_STACK = HRT_BVH_STACK;  // traversal stack entries per lane (LDS); overflow -> exact full scan
+constexpr int BVH_STACK = 24;  // traversal stack entries per lane (LDS); overflow -> exact full scan
 
 // Small culling BVHs (<= LNODE_CAP nodes, depth <= LNODE_DEPTH) are read from LDS by k_trace_split<true>
 // (renderer.cpp decides, the kernel bounds its copy by the same constant).
@@ -82,10 +79,7 @@ constexpr int BVH_STACK = HRT_BVH_STACK;  // traversal stack entries per lane (L
 constexpr uint32_t WATCHDOG = 16, COUNTER_WORDS = 20;
 // the five work counters (queries, box / sphere tests, node / triangle tests) as CSPREAD copies, CSTRIDE words apart:
 // a wave adds its sums to one copy (rt_kernels.hip flush_counts; CSPREAD a power of two), the host adds the copies
-#ifndef HRT_CSPREAD
-#define HRT_CSPREAD 64
-#endif
-constexpr uint32_t CSPREAD = HRT_CSPREAD, CSTRIDE = 16;
+constexpr uint32_t CSPREAD = 64, CSTRIDE = 16;
 // the sample buffer's job queue: NQ counters (one per XCD of MI355X's 8), QSTRIDE words apart (rt_kernels.hip queue_take;
 // renderer.cpp allocates and zeroes NQ x QSTRIDE words)
 constexpr uint32_t NQ = 8, QSTRIDE = 16;
@@ -102,10 +96,7 @@ constexpr uint32_t BVH_MAX_LEAF = 4;
 // k_trace_split<LNODES> also keeps the large list's spheres (16 B each) in LDS; longer lists run the other kernel. 14: the
 // kernel's 22,816 B + 224 B = 23,040 B, a multiple of the 512-B LDS allocation granule that still fits 7 workgroups in
 // the CU's 160 KB (16 entries round up to 23,552 B: the seventh workgroup no longer fits, C3 -2.6 %)
-#ifndef HRT_LLARGE_CAP
-#define HRT_LLARGE_CAP 14
-#endif
-constexpr uint32_t LLARGE_CAP = HRT_LLARGE_CAP;
+constexpr uint32_t LLARGE_CAP = 14;
 
 // Camera-derived constants of make_ray / fs_main, read only when primary rays are generated (once per frame
 // block in the sample queue). The kernels read them through kargs() (below), a pointer to the kernarg segment
@@ -138,7 +129,7 @@ struct KParams {
     const SphereAux* sph_aux;     // per slot
     const SpherePair* sph_pairs;  // per slot pair
     // SCAN_BVH culling structure (host/sphere_bvh.hpp); boxes are relative to bvh_rc
-    const float4* bvh_nodes;      // 4 float4 per node: lmin|left, lmax, rmin|right, rmax
+    const float4* bvh_nodes;      // the f32 nodes: read by no kernel any more; removing the field is DESIGN.md's follow-up
     const float4* bvh_sph;        // leaf spheres in BVH order: cx, cy, cz, r*r
     const int* bvh_slot;          // original slot of each leaf sphere
     const int* large_slots;       // slots scanned linearly for every ray
@@ -146,7 +137,7 @@ struct KParams {
     uint32_t bvh_nleaf, pad_l;    // spheres in the BVH (bvh_sph / bvh_slot entries)
     float bvh_rc[3], bvh_rr;      // root box centre and radius bound
     const uint4* bvh_hnodes;      // the nodes with fp16 boxes, 2 uint4 per node (every sphere-BVH walk;
-                                  // renderer.cpp pack_bvh_hnodes); bvh_nodes is the f32 form (bvh_run<.., false>)
+                                  // renderer.cpp pack_bvh_hnodes)
     float bvh_rr_h;               // radius bound of the fp16 boxes (>= their half-diagonal)
     uint32_t bvh_nnodes;          // nodes in bvh_hnodes
     uint32_t bvh_lnodes;          // 1: k_trace_split keeps the nodes in LDS (<= LNODE_CAP nodes, depth <= 8)
@@ -190,7 +181,7 @@ struct KParams {
     uint32_t tiles_w, tiles_h;    // 8x8 tiles over W x nrows
     uint32_t job_frames, nchunks; // frames per job (a job = one tile x job_frames frames), chunks per tile
     uint32_t suspend_below;       // k_trace_split: suspend the walks once fewer lanes than this still walk (bits 0..7;
-                                  // the sphere program's k_trace_split: bits 8..15 the descent hold, bvh_run<.., HOLD>)
+                                  // the sphere program's k_trace_split: bits 8..15 the descent hold, bvh_walk_noovf<.., HOLD>)
     uint32_t tri_small;           // k_trace_split_tris<.., SMALL>: 16-bit triangle lists + the heap top in LDS
     // frame-block work stealing (k_trace_split / k_trace_split_tris with the sample buffer; rt_kernels.hip steal_block)
     unsigned long long* steal_slots;  // one per wave: (job + 1) << 32 | frames claimed; zeroed per launch

@@ -283,19 +283,6 @@ __device__ __forceinline__ bool padded_box_hit(const float4 mn, const float4 mx,
     return tmin <= tmax;
 }
 
-// padded_box_hit with the best-t bound as a separate compare: tmin <= min(tmax, bt) <=> tmin <= tmax &&
-// tmin <= bt (no NaN here: finite slabs, bt finite), without the per-iteration canonicalize of bt.
-__device__ __forceinline__ bool padded_box_hit_nb(const float4 mn, const float4 mx, const Slab& S, float bt,
-                                                  float& tenter) {
-    const float t0x = __builtin_fmaf(mn.x, S.inv.x, S.lo.x), t1x = __builtin_fmaf(mx.x, S.inv.x, S.hi.x);
-    const float t0y = __builtin_fmaf(mn.y, S.inv.y, S.lo.y), t1y = __builtin_fmaf(mx.y, S.inv.y, S.hi.y);
-    const float t0z = __builtin_fmaf(mn.z, S.inv.z, S.lo.z), t1z = __builtin_fmaf(mx.z, S.inv.z, S.hi.z);
-    const float tmin = fmax_ieee(fmax_ieee(fmin_ieee(t0x, t1x), fmin_ieee(t0y, t1y)), fmax_ieee(fmin_ieee(t0z, t1z), 0.0f));
-    const float tmax = fmin_ieee(fmin_ieee(fmax_ieee(t0x, t1x), fmax_ieee(t0y, t1y)), fmax_ieee(t0z, t1z));
-    tenter = tmin;
-    return tmin <= tmax && tmin <= bt;
-}
-
 // BVH scan, bit-identical to scan_spheres: every sphere the reference could accept lies in a box the
 // padded slab test visits (float-error bound on the discriminant, DESIGN.md §Sphere BVH exactness), every
 // visited sphere is tested with the reference arithmetic, and the winner is the (t, slot) minimum.
@@ -303,8 +290,8 @@ __device__ __forceinline__ bool padded_box_hit_nb(const float4 mn, const float4 
 // back to the full exact scan. `stack` is this lane's slot of the workgroup's LDS stack (stride 256).
 //
 // The query is split in three so a traversal can be suspended and resumed (k_trace_split): bvh_begin
-// (large list, slab constants), bvh_run (the walk; with SUSPEND it returns early once fewer than
-// `below` lanes of the wave are still walking, leaving the state in BvhQuery and the LDS stack) and
+// (large list, slab constants), the walk (bvh_walk_noovf or bvh_walk_ovf; with SUSPEND it returns early once fewer
+// than `below` lanes of the wave are still walking, leaving the state in BvhQuery and the LDS stack) and
 // bvh_end (winner slot, or the exact full scan for the fallback cases).
 struct BvhQuery {
     Slab S;
@@ -321,9 +308,9 @@ __device__ __forceinline__ int bvh_slot_of(const KParams& P, int code) {
 
 template <bool SO, typename RC>
 __device__ __forceinline__ void bvh_slab_k(const Ray& r, BvhQuery& Q, RC rc, float rr, float k1, float k2, float k3, float k4);
-template <bool H16, bool SO>
+template <bool SO>
 __device__ __forceinline__ void bvh_slab(const KParams& P, const Ray& r, BvhQuery& Q) {
-    bvh_slab_k<SO>(r, Q, P.bvh_rc, H16 ? P.bvh_rr_h : P.bvh_rr, P.pad_k1, P.pad_k2, P.pad_k3, P.pad_k4);
+    bvh_slab_k<SO>(r, Q, P.bvh_rc, P.bvh_rr_h, P.pad_k1, P.pad_k2, P.pad_k3, P.pad_k4);
 }
 
 // Returns true when the walk has to run (false: bvh_end does the full scan).
@@ -334,11 +321,11 @@ __device__ __forceinline__ void bvh_slab(const KParams& P, const Ray& r, BvhQuer
 // most LLARGE_CAP entries: every lane reads the same entry, a broadcast) instead of two dependent global loads per
 // sphere and query, and the query's constants (KParams: bq_nlarge .. bq_k4, side by side) through kargs(), so the
 // slab's eight arrive with one wide scalar load and one wait.
-template <bool H16 = false, bool FAST = false, bool KA = false, bool SO = false, bool COUNT = true, bool LLDS = false>
+template <bool FAST = false, bool KA = false, bool SO = false, bool COUNT = true, bool LLDS = false>
 __device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float best, BvhQuery& Q, Tally& tally,
                                           const float4* lgeo = nullptr) {
     const float a = dot(r.d, r.d);
-    const float a4 = 4.0f * a, a2 = 2.0f * a;  // recomputed by bvh_run: fewer registers live across rounds
+    const float a4 = 4.0f * a, a2 = 2.0f * a;  // recomputed by the walk: fewer registers live across rounds
     Q.sp = 0;
     const bool finite_o = __builtin_isfinite(r.o.x) && __builtin_isfinite(r.o.y) && __builtin_isfinite(r.o.z);
     if (!(a2 > 0x1p-100f && a2 < 0x1p100f) || !finite_o) {
@@ -351,18 +338,12 @@ __device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float 
     const uint32_t nleaf = P.bvh_nleaf;
     float bt = best;
     int bc = -1;
-#ifndef HRT_BQ_GROUP
-#define HRT_BQ_GROUP 1
-#endif
     KPtr K = nullptr;
-    if constexpr (LLDS && HRT_BQ_GROUP) K = kargs();
+    if constexpr (LLDS) K = kargs();
     // (KA: loaded per query, not held in SGPRs)
-    const uint32_t nlarge = (LLDS && HRT_BQ_GROUP) ? K->bq_nlarge : KA ? kargs()->nlarge : P.nlarge;
-#ifndef HRT_CAND_T
-#define HRT_CAND_T 2
-#endif
+    const uint32_t nlarge = LLDS ? K->bq_nlarge : KA ? kargs()->nlarge : P.nlarge;
     if constexpr (LLDS) {
-        static_assert(KA && FAST && HRT_CAND_T >= 2, "k_trace_split's begin");
+        static_assert(KA && FAST, "k_trace_split's begin");
         // beats() without the slots: the running winner is a large sphere here (the walk has not run) and the list
         // is in ascending slot order (host/sphere_bvh.hpp), so an equal t later in the list never wins
         for (uint32_t k = 0, n = min(nlarge, LLARGE_CAP); k < n; k++) {
@@ -375,24 +356,23 @@ __device__ __forceinline__ bool bvh_begin(const KParams& P, const Ray& r, float 
     for (uint32_t k = 0; k < nlarge; k++) {  // ascending slots: a later equal t never wins here
         const int i = P.large_slots[k];
         float t;
-        if constexpr (FAST && HRT_CAND_T >= 2) {  // (the root for every lane, selected by the test: no branch around it)
+        if constexpr (FAST) {  // (the root for every lane, selected by the test: no branch around it)
             const float4 g = P.sph_geo[i];
             const bool cand = sphere_candidate(g, r, a4);
             t = candidate_t(g, r, a4, a2, cand);
             t = cand ? t : -1.0f;
         } else {
-            t = exact_t_geo<FAST>(P.sph_geo[i], r, a4, a2);
+            t = exact_t_geo<false>(P.sph_geo[i], r, a4, a2);
         }
         if (beats(t, i, bt, bc >= 0 ? bvh_slot_of(P, bc) : -1)) { bt = t; bc = (int)(nleaf + k); }
     }
     if constexpr (COUNT) tally.spheres += nlarge;
     Q.bt = bt;
     Q.bc = bc;
-    if constexpr (LLDS && HRT_BQ_GROUP) {
-        static_assert(H16, "the side-by-side constants hold the fp16 boxes' radius bound");
+    if constexpr (LLDS) {
         bvh_slab_k<SO>(r, Q, K->bq_rc, K->bq_rr_h, K->bq_k1, K->bq_k2, K->bq_k3, K->bq_k4);
     } else {
-        bvh_slab<H16, SO>(P, r, Q);
+        bvh_slab<SO>(P, r, Q);
     }
     Q.node = P.bvh_root;
     return true;
@@ -425,8 +405,6 @@ __device__ __forceinline__ void bvh_slab_k(const Ray& r, BvhQuery& Q, RC rc, flo
     Q.S.hi = Q.S.hi * Q.S.inv;
 }
 
-// The walk. Returns true when it has finished; with SUSPEND it may return false after a pop, once fewer
-// than `below` lanes of the wave are still walking (every call makes progress: the check follows a pop).
 typedef _Float16 hrt_h2 __attribute__((ext_vector_type(2)));
 // fp16 box decode for the k_trace_split walk (P.bvh_hnodes): the slab FMAs take the halves directly
 // (v_fma_mix_f32: the f16 operand is widened exactly inside the f32 FMA, no conversions).
@@ -445,7 +423,7 @@ __device__ __forceinline__ void load_hnode(const uint4* __restrict__ hn, uint32_
 
 // Sign-ordered padded box test (k_trace_split; the nodes' [min|max] fp16 pairs): each pair rotated by 16 bits where
 // 1/d < 0 (sh = 16) puts the near plane in the low half, so with the near / far constants of bvh_begin<.., SO> the
-// planes' t values are those of padded_box_hit_nb — one FMA per plane, the same roundings — and near <= far without a
+// planes' t values are padded_box_hit's — one FMA per plane, the same roundings — and near <= far without a
 // min / max per axis (min <= max, a bound and its constant order the same way, FMA rounding is monotone; 1/d is never
 // 0 or NaN: robust_inv). One rotate per axis replaces a min and a max: the same visits, bit for bit.
 __device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz, uint32_t shx, uint32_t shy, uint32_t shz,
@@ -461,26 +439,235 @@ __device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz
     return tmin <= tmax && tmin <= bt;
 }
 
-#ifndef HRT_BTEST
-#define HRT_BTEST 1
-#endif
-// NOOVF: the stack cannot overflow — a tree of depth <= STACK (renderer.cpp gates k_trace_split<LNODES> and the
-// mixed kernels' 8-entry stack on depth <= 8): visiting a node of depth d the stack holds at most d entries (one
+// One sphere of a leaf, at BVH position i: the reference's t, and the (t, slot) minimum kept in (bt, bc).
+// FAST (k_trace_split): the sphere and its slot through buffer loads at 32-bit offsets — no 64-bit address kept and
+// stepped per sphere (C3 +0.5 %; the mixed kernels have no SGPRs for the descriptors) — and the range-guarded exact
+// sqrt / division.
+template <bool FAST>
+__device__ __forceinline__ void leaf_sphere_test(const KParams& P, const Ray& r, float a4, float a2, uint32_t i, float& bt,
+                                                 int& bc) {
+    float4 g;
+    if constexpr (FAST) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
+        const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(i * 16u), 0, 0);
+        g = float4{v.x, v.y, v.z, v.w};
+    } else {
+        g = P.bvh_sph[i];
+    }
+    const float t = exact_t_geo<FAST>(g, r, a4, a2);
+    if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
+        int slot;
+        if constexpr (FAST) {
+            const __amdgpu_buffer_rsrc_t rsl =
+                __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
+            slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)(i * 4u), 0, 0);
+        } else {
+            slot = P.bvh_slot[i];
+        }
+        if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)i; }
+    }
+}
+
+// The walk has two forms; a call site names the one it runs (DESIGN.md §The culling walk's two forms). Both read the
+// fp16 nodes `hn` (two uint4 per node, renderer.cpp pack_bvh_hnodes), visit the same nodes in the same order and keep
+// the walk's state in Q and the lane's LDS stack (entry k at stack[k * LS]). Each returns true when the walk has
+// finished; with SUSPEND it may return false after a pop, once fewer than `below` lanes of the wave are still walking
+// (every call makes progress: the check follows a pop).
+//
+// bvh_walk_noovf: the sign-ordered walk of a tree whose depth the stack holds (k_trace_split<LNODES>; the mixed
+// kernels with the heap top in LDS), its descent a bottom-tested loop. Q from bvh_begin<.., SO>.
+// The stack cannot overflow — renderer.cpp gates k_trace_split<LNODES> and the mixed kernels' 8-entry stack on a tree
+// of depth <= 8, as many entries as the stack has: visiting a node of depth d the stack holds at most d entries (one
 // pending sibling per level above it), so a push at an internal node (d <= depth - 1) leaves at most depth. The
 // push then needs no bound check and the walk no overflow flag (5 VALU of a ~50-VALU box step).
-// SO (with H16; Q from bvh_begin<.., SO>): box_hit_so.
-// SW: the stack's entry type, uint32_t or (k_trace_split<LNODES>: HOLD, child words sign-extended from 16 bits, `hn` holds
-// them so) int16_t: the push stores the low half, the pop sign-extends it back.
-template <bool SUSPEND, int STACK = BVH_STACK, bool SELECT = false, bool H16 = false, uint32_t LS = 256,
-          bool NOOVF = false, bool SO = false, bool COUNT = true, bool HOLD = false, typename SW = uint32_t>
-__device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery& Q, SW* stack,
-                                        Tally& tally, uint32_t below, const uint4* __restrict__ hn = nullptr,
-                                        uint32_t hold = 0u) {
-    static_assert(!SO || H16, "the sign-ordered box test reads fp16 pairs");
-    static_assert(!HOLD || (NOOVF && SO && HRT_BTEST), "the descent hold lives in the bottom-tested descent loop");
+// The descent as a bottom-tested loop: one exit (a miss, or a leaf reached) and the node / stack depth updated in
+// place, where the top-tested form (bvh_walk_ovf) keeps two loop-header copies and more exec-mask bookkeeping per box
+// step (C3 +3.2 %). The child order is bvh_walk_ovf's three-way form's.
+// SELECT (k_trace_split): the leaf's spheres in two passes, through buffer loads; else one pass, plain loads.
+// SW: the stack's entry type, uint32_t or (k_trace_split<LNODES> without packets: child words sign-extended from 16
+// bits, `hn` holds them so) int16_t: the push stores the low half, the pop sign-extends it back.
+template <bool SUSPEND, bool SELECT, uint32_t LS, bool COUNT = true, bool HOLD = false, typename SW = uint32_t>
+__device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, BvhQuery& Q, SW* stack, Tally& tally,
+                                               uint32_t below, const uint4* __restrict__ hn, uint32_t hold = 0u) {
     constexpr bool S16 = sizeof(SW) == 2;
-    static_assert(!S16 || HOLD, "16-bit entries: k_trace_split<LNODES>'s walk only");
-    const float4* __restrict__ nodes = P.bvh_nodes;
+    const Slab S = Q.S;
+    // the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds)
+    const uint32_t shx = (__float_as_uint(S.inv.x) >> 27) & 16u, shy = (__float_as_uint(S.inv.y) >> 27) & 16u,
+                   shz = (__float_as_uint(S.inv.z) >> 27) & 16u;
+    const float a = dot(r.d, r.d);  // the same value bvh_begin computed
+    const float a4 = 4.0f * a, a2 = 2.0f * a;
+    uint32_t node = Q.node;
+    int sp = Q.sp;
+    float bt = Q.bt;
+    int bc = Q.bc;
+    // finished is kept as an integer (a VGPR): an i1 lane mask carried through the nested divergent loops of
+    // k_trace_split was observed to go stale (bvh_walk_ovf's overflow flag: sticky full scans)
+    uint32_t finished = 0u;
+#ifdef HRT_STAMPS
+    tally.lentry++;
+    if (first_active_lane()) tally.wentry++;
+#endif
+    while (true) {
+#ifdef HRT_STAMPS
+        tally.lwalk++;
+        if (first_active_lane()) tally.wwalk++;
+#endif
+        // HOLD (k_trace_split; `hold` lanes, 0 = off): the descent loop below runs until its last lane has reached a
+        // leaf or missed, so its late trips run for a handful of lanes while the others wait. With the hold the
+        // whole wave leaves the loop after a step that fewer than `hold` lanes would follow with another one, if
+        // other walking lanes wait: a held lane keeps its internal node, skips the leaf block and the pop, and
+        // takes its next step in the next outer iteration beside the lanes that did pop. Every lane takes the
+        // same steps in the same order (same bits, same test counts, same pushes and pops: the stack bound
+        // stands); only when the wave runs each step changes. lim: the hold clamped to the lanes that entered
+        // this iteration, so a wave whose walking lanes all continue is never held.
+        uint32_t lim = 0u;
+        if constexpr (HOLD) lim = min(hold, (uint32_t)__popcll(__ballot(1)));
+        // A miss leaves BVH_MISS in `node` (all ones, an inline constant: no leaf word — a leaf at 2^27 - 1 would lie
+        // past any sphere buffer; the leaf block skips it, and the pop that follows overwrites it), so "this lane
+        // wants another step" is `node` alone — the loop condition, the hold's count and "held" after the loop —
+        // and no lane mask has to be carried out of the loop.
+        constexpr uint32_t BVH_MISS = 0xFFFFFFFFu;
+        if (!(node & BVH_LEAF_BIT)) {
+            bool any;
+            do {
+#ifdef HRT_STAMPS
+                {
+                    constexpr uint32_t DIAG_LOW = 24u;
+                    const bool low = (uint32_t)__popcll(__ballot(1)) < DIAG_LOW;
+                    tally.lbox++;
+                    tally.lbox_low += low ? 1u : 0u;
+                    if (first_active_lane()) {
+                        tally.wbox++;
+                        tally.wbox_low += low ? 1u : 0u;
+                    }
+                }
+#endif
+                float tl, tr;
+                const uint4 c0 = hn[2 * node], c1 = hn[2 * node + 1];
+                const bool hl = box_hit_so(c0.x, c0.y, c0.z, shx, shy, shz, S, bt, tl);
+                const bool hr = box_hit_so(c1.x, c1.y, c1.z, shx, shy, shz, S, bt, tr);
+                if constexpr (COUNT) tally.boxes += 2;
+                const bool lfirst = hl && (!hr || tl <= tr);
+                const uint32_t near = lfirst ? c0.w : c1.w, far = lfirst ? c1.w : c0.w;
+                const bool both = hl && hr;
+                any = hl || hr;
+                // (the far child is written whether or not it is pushed — one slot past the top when it is
+                // not, never read since sp does not advance, and inside the stack: a box step runs at a node
+                // of depth d <= depth - 1 with sp <= d — so the store needs no branch and exec-mask save)
+                stack[sp * LS] = (SW)far;
+                sp += both ? 1 : 0;
+                node = any ? near : (HOLD ? BVH_MISS : node);
+                if constexpr (HOLD) {
+                    // (the loop condition is the hold's own ballot — emptied by the hold's verdict, a scalar
+                    // select — handed back as a lane predicate, so the exit mask is that scalar mask inverted
+                    // and the node's sign is compared once per step, not twice)
+                    const unsigned long long wants = __builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT));
+                    if (!__builtin_amdgcn_inverse_ballot_w64((uint32_t)__popcll(wants) < lim ? 0ull : wants)) break;
+                } else {
+                    if (!(any && !(node & BVH_LEAF_BIT))) break;
+                }
+            } while (true);
+        }
+        if (HOLD ? (int32_t)node < -1 : (node & BVH_LEAF_BIT) != 0u) {
+#ifdef HRT_STAMPS
+            {
+                constexpr uint32_t DIAG_LOW = 24u;
+                const bool low = (uint32_t)__popcll(__ballot(1)) < DIAG_LOW;
+                tally.lleaf++;
+                tally.lleaf_low += low ? 1u : 0u;
+                if (first_active_lane()) {
+                    tally.wleaf++;
+                    tally.wleaf_low += low ? 1u : 0u;
+                }
+            }
+#endif
+            // (S16: a leaf word is sign-extended from bit 15 — from the LDS nodes or popped — or the root word as built)
+            const uint32_t first = (node >> 4) & (S16 ? 0x7FFu : 0x07FFFFFFu), cnt = node & 15u;
+            if constexpr (SELECT) {
+                // Two passes over the leaf (k_trace_split): the cheap discriminant test of every sphere first, the
+                // lane's candidates (disc >= 0 && b <= 0: 13 % of C3's leaf tests) kept as a bit mask; then the exact
+                // roots of the candidates only. In one pass the root sequence (sqrt, division, the tie check: ~45
+                // instructions) ran for every sphere of the leaf in which ANY walking lane had a candidate — nearly
+                // every one, at a few lanes each; now it runs once per candidate of the lane with the most (mostly
+                // once per leaf). C3 +1.0 % (profiles/r06/leaf_defer/); the mixed kernels' sphere walk (C5, inside
+                // the begin phase) keeps one pass: two passes measured -0.2 % with its IEEE roots, -0.25 % with
+                // these. Exact: the same spheres are tested with the same arithmetic, the (t, slot) minimum does not
+                // depend on the order, and bt (the boxes' bound) is final before the next box step either way.
+                typedef float f4v __attribute__((ext_vector_type(4)));
+                const __amdgpu_buffer_rsrc_t rs =
+                    __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
+                auto leaf_geo = [&](uint32_t o) -> float4 {
+                    const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o, 0, 0);
+                    return float4{v.x, v.y, v.z, v.w};
+                };
+                uint32_t cand = 0u;
+                for (uint32_t o = first * 16u, oe = (first + cnt) * 16u, bit = 1u; o != oe; o += 16u, bit <<= 1) {
+                    if (sphere_candidate(leaf_geo(o), r, a4)) cand |= bit;
+                }
+                while (cand != 0u) {
+                    const uint32_t o = (first + (uint32_t)__builtin_ctz(cand)) * 16u;
+                    cand &= cand - 1u;
+                    const float t = candidate_t(leaf_geo(o), r, a4, a2);
+                    if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
+                        const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
+                            (void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
+                        const int slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)(o >> 2), 0, 0);
+                        if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)(o >> 4); }
+                    }
+                }
+            } else {
+                // one induction variable: the sphere's byte offset (BVH position o / 16)
+                for (uint32_t o = first * 16u, oe = (first + cnt) * 16u; o != oe; o += 16u)
+                    leaf_sphere_test<false>(P, r, a4, a2, o >> 4, bt, bc);
+            }
+            if constexpr (COUNT) tally.spheres += cnt;
+        }
+        // (a held lane — an internal node whose step hit — does not pop and cannot be finished; it counts as
+        // walking in the suspend check, and a suspended Q.node may be that internal node: the entry handles it)
+        if constexpr (HOLD) {  // (k_trace_split's walk; the mixed kernels keep the nested form)
+            // The pop without its branches (as the push's store): the entry below the top — entry 0 for an
+            // empty stack: inside the stack, its value discarded — is read by every lane, and the new node and stack
+            // depth are selects (a held lane keeps both; a finished lane leaves with depth 0). One exit test remains
+            // where the nested form saved the exec mask three times ("not held", "sp != 0", the read). Same pops.
+            const bool held = !(node & BVH_LEAF_BIT);
+            const bool fin = !held && sp == 0;
+            const int spn = max(sp - 1, 0);
+            const uint32_t top = (uint32_t)(int32_t)stack[spn * LS];  // (S16: a sign-extending 16-bit read)
+            node = held ? node : top;
+            sp = held ? sp : spn;
+            if (fin) {
+                finished = 1u;
+                break;
+            }
+        } else {
+            if (sp == 0) {
+                finished = 1u;
+                break;
+            }
+            node = (uint32_t)(int32_t)stack[(--sp) * LS];
+        }
+        if constexpr (SUSPEND) {
+            if ((uint32_t)__popcll(__ballot(1)) < below) break;
+        }
+    }
+    Q.node = node;
+    Q.sp = sp;
+    Q.bt = bt;
+    Q.bc = bc;
+    return finished != 0u;
+}
+
+// bvh_walk_ovf: the general walk, its descent a top-tested loop — any tree: a push is checked against the stack's
+// STACK entries, and an overflow sends the query to the exact full scan (Q.full_scan, bvh_end). k_trace_split without
+// LDS nodes (14 entries), the mixed kernels without the heap top in LDS, closest_hit (k_render, k_trace, k_cast_rays).
+// SO (Q from bvh_begin<.., SO>): box_hit_so; else padded_box_hit on the decoded node.
+// SELECT (k_trace_split): select-form child order, +1 % on C3; the three-way branch keeps k_trace's mixed program
+// (C5) free of spills (the select form spilled 12 VGPRs there, -1.5 %); with it the leaves' spheres as leaf_sphere_test<FAST>.
+template <bool SUSPEND, int STACK, bool SELECT, uint32_t LS, bool SO, bool COUNT = true>
+__device__ __forceinline__ bool bvh_walk_ovf(const KParams& P, const Ray& r, BvhQuery& Q, uint32_t* stack, Tally& tally,
+                                             uint32_t below, const uint4* __restrict__ hn) {
     const Slab S = Q.S;
     // SO: the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds)
     const uint32_t shx = SO ? (__float_as_uint(S.inv.x) >> 27) & 16u : 0u, shy = SO ? (__float_as_uint(S.inv.y) >> 27) & 16u : 0u,
@@ -494,228 +681,6 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
     // overflow and finished are kept as integers (VGPRs): an i1 lane mask carried through the nested
     // divergent loops of k_trace_split was observed to keep stale overflow bits (sticky full scans)
     uint32_t overflow = 0u, finished = 0u;
-#ifndef HRT_LEAFIV
-#define HRT_LEAFIV 1
-#endif
-#ifndef HRT_LEAF_DEFER
-#define HRT_LEAF_DEFER 1
-#endif
-    if constexpr (NOOVF && SO && HRT_BTEST) {
-        // The sign-ordered walks without overflow (k_trace_split with LDS nodes, the HL3 mixed kernels) with the
-        // descent as a bottom-tested loop: one exit (a miss, or a leaf reached) and the node / stack depth updated
-        // in place, where the top-tested form below kept two loop-header copies and more exec-mask bookkeeping
-        // per box step (C3 +3.2 %). Same visits in the same order (the child order is the three-way form's).
-#ifdef HRT_STAMPS
-        tally.lentry++;
-        if (first_active_lane()) tally.wentry++;
-#endif
-        while (true) {
-#ifdef HRT_STAMPS
-            tally.lwalk++;
-            if (first_active_lane()) tally.wwalk++;
-#endif
-            // HOLD (k_trace_split; `hold` lanes, 0 = off): the descent loop below runs until its last lane has reached a
-            // leaf or missed, so its late trips run for a handful of lanes while the others wait. With the hold the
-            // whole wave leaves the loop after a step that fewer than `hold` lanes would follow with another one, if
-            // other walking lanes wait: a held lane keeps its internal node, skips the leaf block and the pop, and
-            // takes its next step in the next outer iteration beside the lanes that did pop. Every lane takes the
-            // same steps in the same order (same bits, same test counts, same pushes and pops: the stack bound
-            // stands); only when the wave runs each step changes. lim: the hold clamped to the lanes that entered
-            // this iteration, so a wave whose walking lanes all continue is never held.
-            uint32_t lim = 0u;
-            if constexpr (HOLD) lim = min(hold, (uint32_t)__popcll(__ballot(1)));
-            // A miss leaves BVH_MISS in `node` (all ones, an inline constant: no leaf word — a leaf at 2^27 - 1 would lie
-            // past any sphere buffer; the leaf block skips it, and the pop that follows overwrites it), so "this lane
-            // wants another step" is `node` alone — the loop condition, the hold's count and "held" after the loop —
-            // and no lane mask has to be carried out of the loop.
-            constexpr uint32_t BVH_MISS = 0xFFFFFFFFu;
-            if (!(node & BVH_LEAF_BIT)) {
-                bool any;
-                do {
-#ifdef HRT_STAMPS
-                    {
-                        constexpr uint32_t DIAG_LOW = 24u;
-                        const bool low = (uint32_t)__popcll(__ballot(1)) < DIAG_LOW;
-                        tally.lbox++;
-                        tally.lbox_low += low ? 1u : 0u;
-                        if (first_active_lane()) {
-                            tally.wbox++;
-                            tally.wbox_low += low ? 1u : 0u;
-                        }
-                    }
-#endif
-                    float tl, tr;
-                    const uint4 c0 = hn[2 * node], c1 = hn[2 * node + 1];
-                    const bool hl = box_hit_so(c0.x, c0.y, c0.z, shx, shy, shz, S, bt, tl);
-                    const bool hr = box_hit_so(c1.x, c1.y, c1.z, shx, shy, shz, S, bt, tr);
-                    if constexpr (COUNT) tally.boxes += 2;
-                    const bool lfirst = hl && (!hr || tl <= tr);
-                    const uint32_t near = lfirst ? c0.w : c1.w, far = lfirst ? c1.w : c0.w;
-                    const bool both = hl && hr;
-                    any = hl || hr;
-#ifndef HRT_PUSH_ALWAYS
-#define HRT_PUSH_ALWAYS 1
-#endif
-                    // (HRT_PUSH_ALWAYS: the far child is written whether or not it is pushed — one slot past the top
-                    // when it is not, never read since sp does not advance, and inside the stack: a box step runs at a
-                    // node of depth d <= depth - 1 with sp <= d — so the store needs no branch and exec-mask save)
-                    if (HRT_PUSH_ALWAYS || both) stack[sp * LS] = (SW)far;
-                    sp += both ? 1 : 0;
-                    node = any ? near : (HOLD ? BVH_MISS : node);
-#ifndef HRT_HOLD_INVB
-#define HRT_HOLD_INVB 1
-#endif
-                    // (HRT_HOLD_INVB: the loop condition is the hold's own ballot — emptied by the hold's verdict, a scalar
-                    // select — handed back as a lane predicate, so the exit mask is that scalar mask inverted and the
-                    // node's sign is compared once per step, not twice)
-                    if constexpr (HOLD && HRT_HOLD_INVB) {
-                        const unsigned long long wants = __builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT));
-                        if (!__builtin_amdgcn_inverse_ballot_w64((uint32_t)__popcll(wants) < lim ? 0ull : wants)) break;
-                    } else {
-                        if constexpr (HOLD) {
-                            if ((uint32_t)__popcll(__builtin_amdgcn_ballot_w64(!(node & BVH_LEAF_BIT))) < lim) break;
-                        }
-                        if (!((HOLD || any) && !(node & BVH_LEAF_BIT))) break;
-                    }
-                } while (true);
-            }
-            if (HOLD ? (int32_t)node < -1 : (node & BVH_LEAF_BIT) != 0u) {
-#ifdef HRT_STAMPS
-                {
-                    constexpr uint32_t DIAG_LOW = 24u;
-                    const bool low = (uint32_t)__popcll(__ballot(1)) < DIAG_LOW;
-                    tally.lleaf++;
-                    tally.lleaf_low += low ? 1u : 0u;
-                    if (first_active_lane()) {
-                        tally.wleaf++;
-                        tally.wleaf_low += low ? 1u : 0u;
-                    }
-                }
-#endif
-                // (S16: a leaf word is sign-extended from bit 15 — from the LDS nodes or popped — or the root word as built)
-                const uint32_t first = (node >> 4) & (S16 ? 0x7FFu : 0x07FFFFFFu), cnt = node & 15u;
-#if HRT_LEAF_DEFER
-                if constexpr (SELECT) {
-                    // Two passes over the leaf (k_trace_split): the cheap discriminant test of every sphere first, the
-                    // lane's candidates (disc >= 0 && b <= 0: 13 % of C3's leaf tests) kept as a bit mask; then the exact
-                    // roots of the candidates only. In one pass the root sequence (sqrt, division, the tie check: ~45
-                    // instructions) ran for every sphere of the leaf in which ANY walking lane had a candidate — nearly
-                    // every one, at a few lanes each; now it runs once per candidate of the lane with the most (mostly
-                    // once per leaf). C3 +1.0 % (profiles/r06/leaf_defer/); the mixed kernels' sphere walk (C5, inside
-                    // the begin phase) keeps one pass: two passes measured -0.2 % with its IEEE roots, -0.25 % with
-                    // these. Exact: the same spheres are tested with the same arithmetic, the (t, slot) minimum does not
-                    // depend on the order, and bt (the boxes' bound) is final before the next box step either way.
-                    typedef float f4v __attribute__((ext_vector_type(4)));
-                    const __amdgpu_buffer_rsrc_t rs =
-                        __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
-                    auto leaf_geo = [&](uint32_t o) -> float4 {
-                        const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o, 0, 0);
-                        return float4{v.x, v.y, v.z, v.w};
-                    };
-                    uint32_t cand = 0u;
-                    for (uint32_t o = first * 16u, oe = (first + cnt) * 16u, bit = 1u; o != oe; o += 16u, bit <<= 1) {
-                        if (sphere_candidate(leaf_geo(o), r, a4)) cand |= bit;
-                    }
-                    while (cand != 0u) {
-                        const uint32_t o = (first + (uint32_t)__builtin_ctz(cand)) * 16u;
-                        cand &= cand - 1u;
-                        const float t = HRT_CAND_T ? candidate_t(leaf_geo(o), r, a4, a2) : exact_t_geo<true>(leaf_geo(o), r, a4, a2);
-                        if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
-                            const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
-                                (void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
-                            const int slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)(o >> 2), 0, 0);
-                            if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)(o >> 4); }
-                        }
-                    }
-                } else
-#endif
-#if HRT_LEAFIV
-                // one induction variable: the sphere's byte offset (slot word at o / 4, BVH position o / 16)
-                for (uint32_t o = first * 16u, oe = (first + cnt) * 16u; o != oe; o += 16u) {
-                    float4 g;
-                    if constexpr (SELECT) {  // (as below: buffer loads and the fast exact division in k_trace_split)
-                        typedef float f4v __attribute__((ext_vector_type(4)));
-                        const __amdgpu_buffer_rsrc_t rs =
-                            __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
-                        const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o, 0, 0);
-                        g = float4{v.x, v.y, v.z, v.w};
-                    } else {
-                        g = P.bvh_sph[o >> 4];
-                    }
-                    const float t = exact_t_geo<SELECT>(g, r, a4, a2);
-                    if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
-                        int slot;
-                        if constexpr (SELECT) {
-                            const __amdgpu_buffer_rsrc_t rsl =
-                                __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
-                            slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)(o >> 2), 0, 0);
-                        } else {
-                            slot = P.bvh_slot[o >> 4];
-                        }
-                        if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)(o >> 4); }
-                    }
-                }
-#else
-                for (uint32_t j = 0; j < cnt; j++) {
-                    float4 g;
-                    if constexpr (SELECT) {  // (as below: buffer loads and the fast exact division in k_trace_split)
-                        typedef float f4v __attribute__((ext_vector_type(4)));
-                        const __amdgpu_buffer_rsrc_t rs =
-                            __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
-                        const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((first + j) * 16u), 0, 0);
-                        g = float4{v.x, v.y, v.z, v.w};
-                    } else {
-                        g = P.bvh_sph[first + j];
-                    }
-                    const float t = exact_t_geo<SELECT>(g, r, a4, a2);
-                    if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
-                        int slot;
-                        if constexpr (SELECT) {
-                            const __amdgpu_buffer_rsrc_t rsl =
-                                __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
-                            slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)((first + j) * 4u), 0, 0);
-                        } else {
-                            slot = P.bvh_slot[first + j];
-                        }
-                        if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)(first + j); }
-                    }
-                }
-#endif
-                if constexpr (COUNT) tally.spheres += cnt;
-            }
-            // (a held lane — an internal node whose step hit — does not pop and cannot be finished; it counts as
-            // walking in the suspend check, and a suspended Q.node may be that internal node: the entry handles it)
-#ifndef HRT_POP_ALWAYS
-#define HRT_POP_ALWAYS 1
-#endif
-            if constexpr (HRT_POP_ALWAYS && HOLD) {  // (k_trace_split's walk; the mixed kernels keep the nested form)
-                // The pop without its branches (as HRT_PUSH_ALWAYS for the push): the entry below the top — entry 0 for an
-                // empty stack: inside the stack, its value discarded — is read by every lane, and the new node and stack
-                // depth are selects (a held lane keeps both; a finished lane leaves with depth 0). One exit test remains
-                // where the nested form saved the exec mask three times ("not held", "sp != 0", the read). Same pops.
-                const bool held = HOLD && !(node & BVH_LEAF_BIT);
-                const bool fin = !held && sp == 0;
-                const int spn = max(sp - 1, 0);
-                const uint32_t top = (uint32_t)(int32_t)stack[spn * LS];  // (S16: a sign-extending 16-bit read)
-                node = held ? node : top;
-                sp = held ? sp : spn;
-                if (fin) {
-                    finished = 1u;
-                    break;
-                }
-            } else
-            if (!(HOLD && !(node & BVH_LEAF_BIT))) {
-                if (sp == 0) {
-                    finished = 1u;
-                    break;
-                }
-                node = (uint32_t)(int32_t)stack[(--sp) * LS];
-            }
-            if constexpr (SUSPEND) {
-                if ((uint32_t)__popcll(__ballot(1)) < below) break;
-            }
-        }
-    } else
     while (true) {
         if (!(node & BVH_LEAF_BIT)) {
 #ifdef HRT_STAMPS
@@ -735,38 +700,18 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
                 right = c1.w;
             } else {
                 float4 n0, n1, n2, n3;
-                if constexpr (H16) {
-                    load_hnode(hn, node, n0, n1, n2, n3);
-                } else {
-                    n0 = nodes[4 * node + 0];
-                    n1 = nodes[4 * node + 1];
-                    n2 = nodes[4 * node + 2];
-                    n3 = nodes[4 * node + 3];
-                }
-                // SELECT (k_trace_split): best-t bound as a separate compare (no per-step canonicalize of bt)
-                // and select-form child order, +1 % on C3; the three-way branch below keeps k_trace's mixed
-                // program (C5) free of spills (the select form spilled 12 VGPRs there, -1.5 %).
-                hl = SELECT ? padded_box_hit_nb(n0, n1, S, bt, tl) : padded_box_hit(n0, n1, S, bt, tl);
-                hr = SELECT ? padded_box_hit_nb(n2, n3, S, bt, tr) : padded_box_hit(n2, n3, S, bt, tr);
+                load_hnode(hn, node, n0, n1, n2, n3);
+                hl = padded_box_hit(n0, n1, S, bt, tl);
+                hr = padded_box_hit(n2, n3, S, bt, tr);
                 left = __float_as_uint(n0.w);
                 right = __float_as_uint(n2.w);
             }
             if constexpr (COUNT) tally.boxes += 2;
-            if constexpr (SELECT && NOOVF) {
-                // (updates written unconditionally: the node and stack depth stay in one register each across the
-                // descent loop instead of being copied at its head)
-                const bool lfirst = hl && (!hr || tl <= tr);
-                const uint32_t near = lfirst ? left : right, far = lfirst ? right : left;
-                const bool both = hl && hr, any = hl || hr;
-                if (both) stack[sp * LS] = far;
-                sp += both ? 1 : 0;
-                node = any ? near : node;
-                if (any) continue;
-            } else if constexpr (SELECT) {
+            if constexpr (SELECT) {
                 const bool lfirst = hl && (!hr || tl <= tr);
                 const uint32_t near = lfirst ? left : right, far = lfirst ? right : left;
                 if (hl && hr) {
-                    if (NOOVF || sp < STACK) {
+                    if (sp < STACK) {
                         stack[sp * LS] = far;
                         sp++;
                     } else {
@@ -777,7 +722,7 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
             } else {
                 if (hl && hr) {
                     const bool lfirst = tl <= tr;
-                    if (NOOVF || sp < STACK) {
+                    if (sp < STACK) {
                         stack[sp * LS] = lfirst ? right : left;
                         sp++;
                     } else {
@@ -797,32 +742,7 @@ __device__ __forceinline__ bool bvh_run(const KParams& P, const Ray& r, BvhQuery
             }
 #endif
             const uint32_t first = (node >> 4) & 0x07FFFFFFu, cnt = node & 15u;
-            for (uint32_t j = 0; j < cnt; j++) {
-                float4 g;
-                if constexpr (SELECT) {  // (k_trace_split) buffer loads at 32-bit offsets: no 64-bit address kept and
-                                         // stepped per sphere (C3 +0.5 %; the mixed kernels have no SGPRs for the
-                                         // descriptors)
-                    typedef float f4v __attribute__((ext_vector_type(4)));
-                    const __amdgpu_buffer_rsrc_t rs =
-                        __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_sph, (short)0, (int)(P.bvh_nleaf * 16u), 0x00020000);
-                    const f4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((first + j) * 16u), 0, 0);
-                    g = float4{v.x, v.y, v.z, v.w};
-                } else {
-                    g = P.bvh_sph[first + j];
-                }
-                const float t = exact_t_geo<SELECT>(g, r, a4, a2);
-                if (t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
-                    int slot;
-                    if constexpr (SELECT) {
-                        const __amdgpu_buffer_rsrc_t rsl =
-                            __builtin_amdgcn_make_buffer_rsrc((void*)P.bvh_slot, (short)0, (int)(P.bvh_nleaf * 4u), 0x00020000);
-                        slot = (int)__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)((first + j) * 4u), 0, 0);
-                    } else {
-                        slot = P.bvh_slot[first + j];
-                    }
-                    if (t < bt || (bc >= 0 && slot < bvh_slot_of(P, bc))) { bt = t; bc = (int)(first + j); }
-                }
-            }
+            for (uint32_t j = 0; j < cnt; j++) leaf_sphere_test<SELECT>(P, r, a4, a2, first + j, bt, bc);
             if constexpr (COUNT) tally.spheres += cnt;
         }
         if (sp == 0) {
@@ -859,12 +779,17 @@ __device__ __forceinline__ int bvh_end(const KParams& P, const Ray& r, const Bvh
     return Q.bc >= 0 ? bvh_slot_of(P, Q.bc) : -1;
 }
 
-template <int STACK = BVH_STACK, bool H16 = true, uint32_t LS = 256, bool KA = false, bool NOOVF = false, bool SO = false>
+// The whole query, walked to completion. NOOVF (the caller's tree is no deeper than the stack; with SO):
+// bvh_walk_noovf, else bvh_walk_ovf with its STACK-entry bound.
+template <int STACK = BVH_STACK, uint32_t LS = 256, bool KA = false, bool NOOVF = false, bool SO = false>
 __device__ __forceinline__ int scan_spheres_bvh(const KParams& P, const Ray& r, float& best, uint32_t* stack,
                                                 Tally& tally) {
+    static_assert(!NOOVF || SO, "bvh_walk_noovf is sign-ordered");
     BvhQuery Q;
-    if (bvh_begin<H16, false, KA, SO>(P, r, best, Q, tally))
-        bvh_run<false, STACK, false, H16, LS, NOOVF, SO>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
+    if (bvh_begin<false, KA, SO>(P, r, best, Q, tally)) {
+        if constexpr (NOOVF) bvh_walk_noovf<false, false, LS>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
+        else bvh_walk_ovf<false, STACK, false, LS, SO>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
+    }
     return bvh_end<KA>(P, r, Q, best, tally);
 }
 
@@ -927,9 +852,9 @@ __device__ __forceinline__ void sphere_record(const KParams& P, const Ray& r, in
 // so each step runs with every lane, the node words come from LDS at one address, and the stack is one VGPR (lane k
 // holds the k-th pending node; depth <= LNODE_DEPTH). Every lane tests every sphere of a visited leaf with the
 // reference arithmetic and keeps the (t, slot) lexicographic minimum, which does not depend on the visiting order.
-// Exact for the same reason bvh_run is: a lane's best t never drops below its winner's t, so the lane's own padded
+// Exact for the same reason the lanes' own walk is: a lane's best t never drops below its winner's t, so the lane's own padded
 // test passes every box on the path to its winner's leaf, the packet visits that leaf, and the lane tests the winner;
-// the spheres the packet adds are real candidates and cannot displace it. Same bits and query count as bvh_run.
+// the spheres the packet adds are real candidates and cannot displace it. Same bits and query count as bvh_walk_noovf.
 template <bool COUNT>
 __device__ __forceinline__ bool packet_walk(const KParams& P, const float4* __restrict__ e, BvhQuery& Q,
                                             const uint4* __restrict__ hn, Tally& tally, bool part) {
@@ -1117,19 +1042,12 @@ __device__ __forceinline__ void tri_record(const KParams& P, const Ray& r, const
     h.front = dot(h.n, r.d) > 0.0f;
 }
 
-#ifndef HRT_TRI_NESTED
-#define HRT_TRI_NESTED 1
-#endif
 // The reference's per-leaf update: accept t in [1e-4, best). The walks only track (best, bj); the hit
 // record is built once for the winner (closest_hit), which keeps fewer registers live during the walk.
 template <bool TBUF = false>
 __device__ __forceinline__ void tri_test(const KParams& P, const Ray& r, uint32_t j, float& best, int& bj) {
     TriDev tr;
     if constexpr (TBUF) {
-#ifndef HRT_TRI_GEO
-#define HRT_TRI_GEO 1
-#endif
-#if HRT_TRI_GEO
         // a, e1, e2 from the compact 36-B operand array (tri_geo) through buffer loads at 32-bit offsets
         typedef uint32_t u3v __attribute__((ext_vector_type(3)));
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)P.tri_geo, (short)0, (int)(P.m * 36u), 0x00020000);
@@ -1139,21 +1057,9 @@ __device__ __forceinline__ void tri_test(const KParams& P, const Ray& r, uint32_
         tr.a = float4{__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), 0.0f};
         tr.e1 = float4{__uint_as_float(e1.x), __uint_as_float(e1.y), __uint_as_float(e1.z), 0.0f};
         tr.e2 = float4{__uint_as_float(e2.x), __uint_as_float(e2.y), __uint_as_float(e2.z), 0.0f};
-#else
-        // a, e1, e2 through buffer loads at 32-bit offsets (no 64-bit address per triangle)
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)P.tris, (short)0, (int)(P.m * 64u), 0x00020000);
-        const f4v a = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(j * 64u), 0, 0);
-        const f4v e1 = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(j * 64u + 16u), 0, 0);
-        const f4v e2 = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(j * 64u + 32u), 0, 0);
-        tr.a = float4{a.x, a.y, a.z, a.w};
-        tr.e1 = float4{e1.x, e1.y, e1.z, e1.w};
-        tr.e2 = float4{e2.x, e2.y, e2.z, e2.w};
-#endif
     } else {
         tr = P.tris[j];
     }
-#if HRT_TRI_NESTED
     // tri_t's tests as nested branches (no -1 sentinel carried to a merge: its moves and select per triangle)
     const f3 e1 = mk(tr.e1.x, tr.e1.y, tr.e1.z);
     const f3 e2 = mk(tr.e2.x, tr.e2.y, tr.e2.z);
@@ -1169,9 +1075,6 @@ __device__ __forceinline__ void tri_test(const KParams& P, const Ray& r, uint32_
     const float v = inv_det * dot(r.d, q);
     if (v < 0.0f || u + v > 1.0f) return;
     const float t = inv_det * dot(e2, q);
-#else
-    const float t = tri_t(r, tr);
-#endif
     if (t >= 1e-4f && t < best) {
         best = t;
         bj = (int)j;
@@ -1255,7 +1158,7 @@ __device__ __forceinline__ bool heap_run(const KParams& P, const Ray& r, HeapWal
     const uint32_t n = P.n, m = P.m;
     uint32_t i = W.i, step = W.step, nc = 0u;
     const uint32_t step0 = step, tris0 = tally.tris;
-    uint32_t walking = 1u;  // an integer, not an i1 lane mask (see bvh_run)
+    uint32_t walking = 1u;  // an integer, not an i1 lane mask (see bvh_walk_ovf)
     float best = W.best;
     int bj = W.bj;
     if (i >= n) {  // n == 1: the root is leaf 0, the walk's only body (heap_begin starts every walk at i = 1)
@@ -1352,7 +1255,7 @@ __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, flo
     S.hi = S.hi * S.inv;
     uint32_t node = P->tb_root;  // bj: index of the best triangle (-1: none, or the best is a sphere)
     int sp = 0;
-    uint32_t overflow = 0u;  // an integer, not an i1 lane mask (see bvh_run)
+    uint32_t overflow = 0u;  // an integer, not an i1 lane mask (see bvh_walk_ovf)
     while (true) {
         if (!(node & BVH_LEAF_BIT)) {
             float4 n0, n1, n2, n3;
@@ -1410,7 +1313,7 @@ __device__ __forceinline__ bool closest_hit(const KParams& P, const Ray& r, Hit&
     if (MODE != MODE_TRIS) {
         if constexpr (SCAN == SCAN_BVH) {
             // (with the SAH triangle walk the sphere walk's rare-path constants are read through kargs(): 0 SGPR spills)
-            bi = scan_spheres_bvh<BVH_STACK, true, 256, TSAH>(P, r, best, (uint32_t*)lds, tally);
+            bi = scan_spheres_bvh<BVH_STACK, 256, TSAH>(P, r, best, (uint32_t*)lds, tally);
         } else if constexpr (SCAN == SCAN_DEFER) {
             bi = scan_spheres_deferred(P, r, best, (uint16_t*)lds);
             tally.spheres += P.nslots;
@@ -1824,16 +1727,12 @@ struct WaveJobs {
 // helpers below that differ by it (RING; the launchers pick by P.ring_mode), so a sample-buffer kernel holds none of
 // the ring's code and reads no mode word: every bench configuration draws with the sample buffer,
 // and k_trace_split paid for the ring with about six scalar-load round trips of ring_mode per round (DESIGN.md §4
-// Round 9). The helpers take it as an int: 0, 1, or FOLD_DYN, the mode tested at run time as before round 9 — the packet
-// kernels (their register budget is another; the ring + counting one spilled when specialised), and every kernel with
-// HRT_FOLD_TEMPLATE 0 (A/B builds).
-#ifndef HRT_FOLD_TEMPLATE
-#define HRT_FOLD_TEMPLATE 1
-#endif
+// Round 9). The helpers take it as an int: 0, 1, or FOLD_DYN, the mode tested at run time — the packet kernels (their
+// register budget is another; the ring + counting one spilled when specialised).
 constexpr int FOLD_DYN = 2;
 template <int RING>
 __device__ __forceinline__ bool fold_ring() {
-    if constexpr (HRT_FOLD_TEMPLATE && RING != FOLD_DYN) return RING != 0;
+    if constexpr (RING != FOLD_DYN) return RING != 0;
     else return kargs()->ring_mode != 0u;
 }
 
@@ -1873,9 +1772,9 @@ __device__ __forceinline__ void ring_store(const WaveJobs& J, uint32_t pix, uint
 // tile's frame 0, frame f at tile + f * fstride; the lane's pixel is 3 floats at lane3. U frames' loads are issued
 // before their mixes (a wave's frame is 768 B: one load in flight per wave left k_accumulate latency-bound); the
 // uniform frame address + a 32-bit lane offset keeps each load to one VGPR of address (global_load saddr).
-template <int U>
 __device__ __forceinline__ void fold_pixel(float* px, const float* tile, uint32_t lane3, size_t fstride, uint32_t nframes,
                                            uint32_t frame0, float ema_cap) {
+    constexpr int U = 8;
     float acc0 = px[0], acc1 = px[1], acc2 = px[2];
     uint32_t f = 0;
     for (; f + (uint32_t)U <= nframes; f += (uint32_t)U, tile += (size_t)U * fstride) {
@@ -1931,7 +1830,7 @@ __device__ __forceinline__ void fold_prev_tiles(const KParams& P, uint32_t lane)
         const uint32_t x = (t % P.tiles_w) * 8u + (lane & 7u);
         const uint32_t kr = (t / P.tiles_w) * 8u + (lane >> 3);
         if (x < P.W && kr < P.nrows)
-            fold_pixel<8>(P.image + ((size_t)kr * P.W + x) * 3u, P.fold_prev + (size_t)t * 192u, lane * 3u, npad3,
+            fold_pixel(P.image + ((size_t)kr * P.W + x) * 3u, P.fold_prev + (size_t)t * 192u, lane * 3u, npad3,
                           P.fold_nframes, P.fold_frame0, P.ema_cap);
     }
 }
@@ -2181,28 +2080,18 @@ __device__ __forceinline__ void job_account(const WaveJobs& J, bool fin, uint32_
 // stealing for < 2^25 - 1 tiles and < 2^11 chunks; claims stop once a slot reads exhausted, so the 16-bit count
 // stays far below its field's end). Wave state in the WaveJobs words the sample buffer leaves unused: flags (own
 // job, queue drained, lost race), the last victim, and the claimed frames not dealt yet.
-#ifndef HRT_STEAL_OWN
-#define HRT_STEAL_OWN 1  // (4 before round 5: the owner's claims of 4 frames held them from idle thieves in the tail;
-                         // 4 only for jobs dealt early, while the queue holds > 2 jobs per wave: C4 8-way 0.756 -> 0.70,
-                         // the early jobs still running at the drain are the long ones, profiles/r05/p/)
-#endif
-#ifndef HRT_CLAIM_FREE
-#define HRT_CLAIM_FREE 32
-#endif
-constexpr uint32_t STEAL_OWN = HRT_STEAL_OWN;
+// (STEAL_OWN 4: the owner's claims of 4 frames held them from idle thieves in the tail; 4 only for jobs dealt early,
+// while the queue holds > 2 jobs per wave: C4 8-way 0.756 -> 0.70, the early jobs still running at the drain are the
+// long ones, profiles/r05/p/)
+constexpr uint32_t STEAL_OWN = 1;
 constexpr uint32_t ST_OWN = 1u, ST_QEMPTY = 2u, ST_RETRY = 4u;
 // The tail (round 5): once the job queue is drained, a wave whose lanes are not all free claims another frame block only
 // when at least CLAIM_FREE of them are. A block claimed for a few free lanes waits for this wave's busy ones (paths of
 // up to 50 bounces) while other waves have run dry and exited: C4's 1/8 share drained its queue at 18.1 ms and ran to
 // 23.5 ms (`scripts/wave_tail.py`, profiles/r05/). A wave with every lane free always claims, so the launch drains.
-constexpr uint32_t CLAIM_FREE = HRT_CLAIM_FREE;
+constexpr uint32_t CLAIM_FREE = 32;
 // The same rule for a wave that has dealt a tail part (job_acquire<TAIL>, no stealing): its next part waits for
-// CLAIM_FREE free lanes (HRT_TAIL_CLAIM 0 = round 4: a part for any free lane).
-#ifndef HRT_TAIL_CLAIM
-#define HRT_TAIL_CLAIM 1
-#endif
-constexpr bool TAIL_CLAIM = HRT_TAIL_CLAIM != 0;
-
+// CLAIM_FREE free lanes.
 
 enum : uint32_t { WJ_ST = WJ_TILE, WJ_VICTIM = WJ_TILE + 1, WJ_PRIV_F = WJ_TILE + 2, WJ_PRIV_N = WJ_TILE + 3,
                   WJ_CLAIM_F = WJ_F0, WJ_CLAIM_T = WJ_LIVE };
@@ -2380,10 +2269,7 @@ __device__ __forceinline__ void refill_block(const KParams& P, BlockQueue& B, co
             B.pr_ok = (x < P.W && kr < P.nrows) ? 1u : 0u;  // ragged edge tiles: no sample
             if (B.pr_ok) {
                 const uint32_t y = global_row(P.row0, P.row_block, P.row_stride, kr);
-#ifndef HRT_UGUARD_KTRACE_PRIMARY
-#define HRT_UGUARD_KTRACE_PRIMARY 1
-#endif
-                const Ray pr = primary_ray<MODE, MODE == MODE_SPHERE, MODE == MODE_SPHERE && HRT_UGUARD_KTRACE_PRIMARY != 0>(
+                const Ray pr = primary_ray<MODE, MODE == MODE_SPHERE, MODE == MODE_SPHERE>(
                     &kargs()->cam, x, y, P.time0 + (B.job_f0 + B.blk_f) * P.dtime, B.pr_s);
                 B.pr_o = pr.o;
                 B.pr_d = pr.d;
@@ -2694,9 +2580,6 @@ struct BlockState {
     uint32_t nblocks = 0;  // (diagnostic build: frame blocks this wave generated, for its wave record)
 #endif
 };
-#ifndef HRT_UGUARD_KTRACE
-#define HRT_UGUARD_KTRACE 1  // (k_trace's sphere program: the exact sequences' guards as wave-uniform branches)
-#endif
 // (the body of k_trace and k_ring: the two fold modes, below)
 template <int MODE, int SCAN, bool TSAH, bool RING>
 __device__ __forceinline__ void trace_queue(const KParams& P) {
@@ -2798,7 +2681,7 @@ __device__ __forceinline__ void trace_queue(const KParams& P) {
 #ifdef HRT_STAMPS
             const uint32_t boxes0 = tally.boxes;
 #endif
-            constexpr bool UG = MODE == MODE_SPHERE && HRT_UGUARD_KTRACE != 0;
+            constexpr bool UG = MODE == MODE_SPHERE;  // (the sphere program: the exact sequences' guards as wave-uniform branches)
             const bool hit = closest_hit<MODE, SCAN, TSAH, UG>(P, ray, h, lds_list, tally, tri_cand, tri_stack);
             queries++;
 #ifdef HRT_STAMPS
@@ -2876,23 +2759,15 @@ __device__ __forceinline__ void trace_queue(const KParams& P) {
 // rt_stats.fold_ring the mode.
 // 6 waves per SIMD: the register budget is 80 VGPRs (84 unconstrained = 5 waves; measured +8% on C3)
 // (the mixed program's deferred scan holds 32 KB of LDS per workgroup: 5 waves/SIMD whatever the VGPRs)
-// (HRT_KTRACE_PIN 1, A/B builds: the target as the maximum too — with the fold mode compiled in the linear scans need
-// 60 VGPRs and run 8 waves per SIMD where the runtime-switched kernel ran 6)
-#ifndef HRT_KTRACE_PIN
-#define HRT_KTRACE_PIN 0
-#endif
-#if HRT_KTRACE_PIN
-#define HRT_KTRACE_WAVES(w) amdgpu_waves_per_eu(w, w)
-#else
-#define HRT_KTRACE_WAVES(w) amdgpu_waves_per_eu(w)
-#endif
+// (a target, not a maximum: with the fold mode compiled in the linear scans need 60 VGPRs and run 8 waves per SIMD
+// where the runtime-switched kernel ran 6)
 template <int MODE, int SCAN, bool TSAH = false>
-__global__ __launch_bounds__(256) __attribute__((HRT_KTRACE_WAVES(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     (TSAH || (MODE == MODE_MIXED && SCAN == SCAN_DEFER) ? 5 : 6)))) void k_trace(const KParams P) {
     trace_queue<MODE, SCAN, TSAH, false>(P);
 }
 template <int MODE, int SCAN, bool TSAH = false>
-__global__ __launch_bounds__(256) __attribute__((HRT_KTRACE_WAVES(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     (TSAH || (MODE == MODE_MIXED && SCAN == SCAN_DEFER) ? 5 : 6)))) void k_ring(const KParams P) {
     trace_queue<MODE, SCAN, TSAH, true>(P);
 }
@@ -2937,7 +2812,7 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
                     B.blk_f++;
                 } else {
                     // (the tail: once this wave dealt a tail part, a new one only for CLAIM_FREE free lanes, as stealing)
-                    if (TAIL_CLAIM && (J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull) break;
+                    if ((J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull) break;
                     if (!job_acquire<RING, true>(J, lane, drained, B.job_tile, B.job_f0, B.job_nf)) break;
                     B.blk_f = 0;
                 }
@@ -3059,7 +2934,7 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
 // (BvhQuery in registers, stack in LDS), as soon as fewer than `suspend_below` lanes of the wave are still
 // walking; the finished lanes shade, start their next query (or sample) and all lanes walk on together.
 // Every lane computes exactly the same query as k_trace, so the sample colours are bit-identical.
-// 7 waves per SIMD (72-VGPR budget, no spills since bvh_run recomputes a = d.d instead of carrying it): the
+// 7 waves per SIMD (72-VGPR budget, no spills since the walk recomputes a = d.d instead of carrying it): the
 // frame block lives in LDS (8 KB per workgroup)
 // next to a 14-entry stack (14 KB), 22 KB x 7 workgroups fitting the CU's 160 KB. Measured on C3: block in
 // VGPRs at 6 waves (20-entry stack) 26.1 Grays/s, block in LDS at 7 waves 26.5; per-lane primary rays were
@@ -3080,26 +2955,11 @@ __device__ __forceinline__ void refill_block_lds(const KParams& P, BlockState& B
 // by 4 KB, to 8 x 18.5 KB per CU.
 // 8 waves per SIMD (split_waves) for the sample-buffer kernels without counting, stealing and packets: with the ring
 // compiled out they fit 64 VGPRs without scratch. The others keep 7 (12 to 52 B of scratch at 64 VGPRs).
-#ifndef HRT_STACK16
-#define HRT_STACK16 1
-#endif
-#ifndef HRT_SPLIT_WAVES8
-#define HRT_SPLIT_WAVES8 1
-#endif
-#ifndef HRT_PACKET_WAVES
-#define HRT_PACKET_WAVES 7
-#endif
-#ifndef HRT_PACKET_STEAL_WAVES
-#define HRT_PACKET_STEAL_WAVES 6  // (the stealing packet kernel spills 6 VGPRs at 7 waves)
-#endif
-#ifndef HRT_SPLIT_WAVES
-#define HRT_SPLIT_WAVES 7
-#endif
-constexpr bool split_stack16(bool lnodes, bool packet) { return HRT_STACK16 && lnodes && !packet; }
+constexpr bool split_stack16(bool lnodes, bool packet) { return lnodes && !packet; }
 // (8 only where the workgroup's LDS leaves room for an eighth, the 16-bit stack, and with the fold mode compiled in)
 constexpr int split_waves(bool lnodes, bool steal, bool count, bool packet, bool ring) {
-    if (packet) return steal ? HRT_PACKET_STEAL_WAVES : HRT_PACKET_WAVES;
-    return HRT_SPLIT_WAVES8 && HRT_FOLD_TEMPLATE && split_stack16(lnodes, packet) && !steal && !count && !ring ? 8 : HRT_SPLIT_WAVES;
+    if (packet) return steal ? 6 : 7;  // (the stealing packet kernel spills 6 VGPRs at 7 waves)
+    return split_stack16(lnodes, packet) && !steal && !count && !ring ? 8 : 7;
 }
 template <bool LNODES, bool STEAL, bool COUNT, bool PACKET, bool RING>
 __device__ __forceinline__ void trace_split(const KParams& P) {
@@ -3108,11 +2968,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     constexpr int FM = PACKET ? FOLD_DYN : (int)RING;  // (the packet kernels: one instantiation for both fold modes)
     static_assert(!(PACKET && RING) && !(STEAL && RING), "no such instantiation: launch_trace_split");
     constexpr int SPLIT_STACK = LNODES ? (int)LNODE_DEPTH : 14;
-#ifndef HRT_SHADE_BY_CODE
-#define HRT_SHADE_BY_CODE 1
-#endif
     // (the packet kernels' block entries carry the winner's slot: they shade from the slot table)
-    constexpr bool SHADE_BY_CODE = HRT_SHADE_BY_CODE && !PACKET;
+    constexpr bool SHADE_BY_CODE = !PACKET;
     const uint32_t lane = threadIdx.x & 63u;
     constexpr bool STACK16 = split_stack16(LNODES, PACKET);
     static_assert(!STACK16 || (LNODE_CAP <= 0x8000u && (LNODE_CAP + 1u) * BVH_MAX_LEAF <= 2048u),
@@ -3120,11 +2977,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     using StackWord = std::conditional_t<STACK16, int16_t, uint32_t>;
     __shared__ StackWord bvh_stack[SPLIT_STACK * 256];
     __shared__ uint4 lnodes[LNODES ? 2 * LNODE_CAP : 1];
-#ifndef HRT_LLARGE_LDS
-#define HRT_LLARGE_LDS 1
-#endif
     // (the packet kernels keep the global large list: their register budget is another; out of this change's scope)
-    constexpr bool LLDS = HRT_LLARGE_LDS && LNODES && !PACKET;
+    constexpr bool LLDS = LNODES && !PACKET;
     __shared__ float4 lgeo[LLDS ? LLARGE_CAP : 1];  // the large list's spheres: (cx, cy, cz, r*r), in list order
     if constexpr (LNODES) {
         const uint32_t nn = 2u * min(P.bvh_nnodes, LNODE_CAP);  // renderer.cpp gates LNODES on the same cap
@@ -3195,7 +3049,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                         blk_f++;
                     } else {
                         // (the tail: once this wave dealt a tail part, a new one only for CLAIM_FREE free lanes, as stealing)
-                        if (TAIL_CLAIM && (J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull)
+                        if ((J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull)
                             break;
                         if (!job_acquire<FM, true>(J, lane, drained, job_tile, job_f0, job_nf)) break;
                         blk_f = 0;
@@ -3220,10 +3074,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 blk[2 * threadIdx.x + 1] = float4{pr.d.y, pr.d.z, __uint_as_float(ps), __uint_as_float(ew)};
                 if constexpr (PACKET) {
                     // (bounce cap 0: no query; rays bvh_begin leaves to the full scan: resolved later, qs 0)
-#ifndef HRT_PACKET_DRY
-#define HRT_PACKET_DRY 0  // (A/B builds only: 1 = the packet kernel without its walk, every primary ray unresolved)
-#endif
-                    if (P.bounces > 0u && !HRT_PACKET_DRY) {  // (wave-uniform: every lane enters the packet walk)
+                    if (P.bounces > 0u) {  // (wave-uniform: every lane enters the packet walk)
                         BvhQuery Qp;
                         // slab constants only (bvh_begin's uncovered-ray rule); the large list after the walk: the
                         // (t, slot) minimum does not depend on the order, and the walk then holds fewer registers
@@ -3232,7 +3083,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                                          __builtin_isfinite(pr.o.y) && __builtin_isfinite(pr.o.z);
                         Qp.bt = cov ? FLT_MAX_REF : -1.0f;  // (-1: no test passes)
                         Qp.bc = -1;
-                        bvh_slab<true, true>(P, pr, Qp);
+                        bvh_slab<true>(P, pr, Qp);
                         if (packet_walk<COUNT>(P, blk + 2 * threadIdx.x, Qp, lnodes, tally, cov) && cov) {
                             // the entry: the hit point in place of the origin and the winner's slot, or a resolved miss
                             // (everything re-read from the entry: nothing of the block kept in registers through the walk)
@@ -3320,7 +3171,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         HRT_LANES(0, have && qs == 0u);
         if (have && qs == 0u) {
             if (bounce < P.bounces) {
-                qs = bvh_begin<true, true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : 2u;
+                qs = bvh_begin<true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : 2u;
             } else {  // bounce cap 0: the sample is the sky colour
                 qs = 3u;
             }
@@ -3329,10 +3180,10 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         HRT_LANES(1, have && qs == 1u);
         if (have && qs == 1u) {
             if constexpr (LNODES) {  // (depth <= LNODE_DEPTH = SPLIT_STACK: no overflow)
-                if (bvh_run<true, SPLIT_STACK, true, true, 256, true, true, COUNT, !PACKET>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
+                if (bvh_walk_noovf<true, true, 256, COUNT, !PACKET>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
                     qs = 2u;
             } else {
-                if (bvh_run<true, SPLIT_STACK, true, true, 256, false, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))
+                if (bvh_walk_ovf<true, SPLIT_STACK, true, 256, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))
                     qs = 2u;
             }
         }
@@ -3372,12 +3223,9 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 if constexpr (!PACKET) queries++;
                 if (bi >= 0) {
                     Hit h;
-#ifndef HRT_UGUARD
-#define HRT_UGUARD 1
-#endif
                     const SphereAux* __restrict__ tab = SHADE_BY_CODE ? P.code_aux : nullptr;
-                    sphere_record_p<HRT_UGUARD != 0>(P, p, ray.d, bi, best, h, tab);
-                    scatter<MODE, HRT_UGUARD != 0>(P, s, ray, h, tab);
+                    sphere_record_p<true>(P, p, ray.d, bi, best, h, tab);
+                    scatter<MODE, true>(P, s, ray, h, tab);  // (both: the guards as wave-uniform branches)
                     att = att * mk(h.ar * 0.7f, h.ag * 0.7f, h.ab * 0.7f);
                     bounce++;
                     done = bounce >= P.bounces;
@@ -3458,12 +3306,6 @@ constexpr uint32_t heap_wg(int hl) { return hl == 3 ? 768u : 256u; }
 constexpr uint32_t heap_list_words(int hl, int scan) { return hl == 0 ? TRI_BATCH : (hl == 3 && scan != SCAN_BVH) ? 7u : 8u; }
 constexpr uint32_t heap_top_n(int hl, int scan) { return hl == 0 ? 0u : hl == 1 ? 256u : 1024u; }
 
-#ifndef HRT_HEAP_FAST_BVH
-#define HRT_HEAP_FAST_BVH 0  // (1: the culling-BVH mixed kernel (C5) takes heap_begin's refined reciprocals too: -0.2 %)
-#endif
-#ifndef HRT_UGUARD_TRIS
-#define HRT_UGUARD_TRIS 1  // (the mixed kernels' sphere hit record with the linear scan (C4): its normal division's guard as
-#endif                     //  a wave-uniform branch, +0.3 %; with the culling BVH (C5) -0.1 %, so not there)
 template <int MODE, int SCAN, int HL, bool STEAL, bool RING>
 __device__ __forceinline__ void trace_split_tris(const KParams& P) {
     static_assert(MODE != MODE_SPHERE, "k_trace_split covers the sphere program");
@@ -3542,11 +3384,12 @@ __device__ __forceinline__ void trace_split_tris(const KParams& P) {
                 float sb = FLT_MAX_REF;
                 int bi;
                 // (HL > 0: renderer.cpp runs these only for sphere trees of depth <= 8 = SPHERE_STACK: no overflow)
-                if constexpr (SCAN == SCAN_BVH) bi = scan_spheres_bvh<SPHERE_STACK, true, WGT, true, (HL > 0), true>(P, ray, sb, sstack, tally);
+                if constexpr (SCAN == SCAN_BVH) bi = scan_spheres_bvh<SPHERE_STACK, WGT, true, (HL > 0), true>(P, ray, sb, sstack, tally);
                 else if constexpr (SCAN == SCAN_DEFER) bi = scan_spheres_deferred(P, ray, sb, defer_list);
                 else bi = scan_spheres(P, ray, sb);
                 if constexpr (SCAN != SCAN_BVH) tally.spheres += P.nslots;  // the BVH scan counts its own
-                heap_begin<SCAN != SCAN_BVH || HRT_HEAP_FAST_BVH != 0>(ray, sb, W);
+                // (the culling-BVH mixed kernel (C5) keeps the IEEE divisions: heap_begin's refined reciprocals measured -0.2 %)
+                heap_begin<SCAN != SCAN_BVH>(ray, sb, W);
                 W.bj = -2 - bi;
                 qs = 3u;
             }
@@ -3582,8 +3425,10 @@ __device__ __forceinline__ void trace_split_tris(const KParams& P) {
                 queries++;
                 Hit h;
                 bool hit = true;
+                // (the sphere hit record with the linear scan (C4): its normal division's guard as a wave-uniform branch,
+                // +0.3 %; with the culling BVH (C5) -0.1 %, so not there)
                 if (W.bj >= 0) tri_record(P, ray, P.tris[W.bj], W.best, h);
-                else if (W.bj <= -2) sphere_record<HRT_UGUARD_TRIS != 0 && SCAN != SCAN_BVH>(P, ray, -2 - W.bj, W.best, h);
+                else if (W.bj <= -2) sphere_record<SCAN != SCAN_BVH>(P, ray, -2 - W.bj, W.best, h);
                 else hit = false;
                 if (hit) {
                     scatter<MODE>(P, s, ray, h);
@@ -3659,7 +3504,7 @@ __global__ __launch_bounds__(256) void k_accumulate(const KParams P) {
     const uint32_t kr = (tile / P.tiles_w) * 8u + (l >> 3);
     if (x >= P.W || kr >= P.nrows) return;
     const uint32_t wtile = __builtin_amdgcn_readfirstlane(tile);  // (a wave is one tile)
-    fold_pixel<8>(P.image + ((size_t)kr * P.W + x) * 3u, P.samples + (size_t)wtile * 192u, l * 3u, npad * 3u, P.nframes,
+    fold_pixel(P.image + ((size_t)kr * P.W + x) * 3u, P.samples + (size_t)wtile * 192u, l * 3u, npad * 3u, P.nframes,
                   P.frame0, P.ema_cap);
 }
 
@@ -3679,10 +3524,8 @@ hipError_t hrt_launch_accumulate(const KParams& P, hipStream_t stream) {
 // (C4 -2.3 %, C2 -5 %, C3 -0.8 % on full images: the rays of a band of adjacent tiles share their scene data in the
 // caches); the head's expensive tiles cluster on the same objects. Which wave traces a sample never changes its colour
 // or its place in the sample buffer, so the image is bit-identical in any order.
-#ifndef HRT_ORDER_HEAD_PCT
-#define HRT_ORDER_HEAD_PCT 50  // (12 / 25 / 50 / 100: C4 8-way 0.82 / 0.82 / 0.84 / 0.83, C2 0.66 / 0.65 / 0.66 / 0.65; profiles/r05/v/)
-#endif
-constexpr uint32_t ORDER_BUCKETS = 128, ORDER_HEAD_PCT = HRT_ORDER_HEAD_PCT, ORDER_BLOCK = 1024;
+// (ORDER_HEAD_PCT 12 / 25 / 50 / 100: C4 8-way 0.82 / 0.82 / 0.84 / 0.83, C2 0.66 / 0.65 / 0.66 / 0.65; profiles/r05/v/)
+constexpr uint32_t ORDER_BUCKETS = 128, ORDER_HEAD_PCT = 50, ORDER_BLOCK = 1024;
 __device__ __forceinline__ uint32_t order_bucket(uint32_t cost) {
     // floor(4 * log2(cost + 1)) from the float's exponent and top two significand bits (cost + 1 >= 1, <= 2^32: the
     // class of 2^32 is clamped), most expensive first

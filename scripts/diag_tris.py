@@ -4,7 +4,7 @@ Run on the GPU box after `make -C hello-raytracing_amd diag`:
     HRT_LIB=lib/libhrt_diag.so python scripts/diag_tris.py [--frames 16]
 
 For C5's scene (4K, the bench's knobs) prints the sphere walk's lanes per box / leaf step, the lanes that enter it per
-walk, and the share of its wave steps run with fewer than 24 lanes (DIAG_LOW in bvh_run) — the part of the walk a
+walk, and the share of its wave steps run with fewer than 24 lanes (DIAG_LOW in bvh_walk_noovf) — the part of the walk a
 suspendable sphere walk (threshold 24, as the heap walk's) would move into fuller steps.
 """
 import argparse

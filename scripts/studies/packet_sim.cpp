@@ -3,7 +3,7 @@
 //
 // For sampled 8x8 tiles x frames of a sphere scene it generates the reference's primary rays (the oracle's make_ray,
 // oracle/rt_oracle.c) and traces every sample's whole path with the oracle's closest hit. For every query it counts
-// what today's per-lane walk does (k_trace_split's bvh_run: near child first, a child visited when its box is entered
+// what today's per-lane walk does (k_trace_split's bvh_walk_noovf: near child first, a child visited when its box is entered
 // no later than the lane's best t; the large list scanned first), and for the primary rays of a block what a
 // wave-uniform walk of the union of the 64 lanes' nodes does (a child visited when any lane enters it; every lane
 // tests every sphere of a visited leaf). Boxes are the builder's f32 boxes unpadded — a model, not the kernel's
@@ -63,7 +63,7 @@ static float large_best(const o_scene* sc, v3 o, v3 d) {
     return bt;
 }
 
-// today's walk for one ray (bvh_run: near child first, far pushed)
+// today's walk for one ray (bvh_walk_noovf: near child first, far pushed)
 static void lane_walk(const o_scene* sc, v3 o, v3 d, Stats& S) {
     float a = dot3(d, d), bt = large_best(sc, o, d);
     v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);

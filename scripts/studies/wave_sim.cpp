@@ -7,7 +7,7 @@
 //           a random 8x8 tile x `job_frames` consecutive frames (time 1000 + 10 f); entries outside the image are
 //           consumed and give no sample.
 //   begin   lanes that start a query (the large list, the slab constants).
-//   walk    bvh_run, step by step for the whole wave: outer iterations of descent -> leaf -> pop. The descent loop runs
+//   walk    bvh_walk_noovf, step by step for the whole wave: outer iterations of descent -> leaf -> pop. The descent loop runs
 //           while any lane wants another box step; `hold` > 0 is the descent hold (the wave leaves the loop after a step
 //           that fewer than min(hold, lanes that entered the iteration) lanes would follow with another one; the
 //           stragglers keep their node, skip the pop, and step in the next iteration). After the pop the walk is
@@ -131,7 +131,7 @@ struct Sim {
         cnt_out = cnt, cand_out = cand;
     }
 
-    // bvh_run for the lanes of `w` (qs == 1), in lockstep
+    // bvh_walk_noovf for the lanes of `w` (qs == 1), in lockstep
     void walk(Lane* lanes, const std::vector<int>& w) {
         std::vector<int> act = w;  // lanes still in this call
         C.wcall++, C.lcall += act.size();

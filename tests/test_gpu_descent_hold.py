@@ -1,4 +1,4 @@
-"""The descent hold of k_trace_split's culling walk (bvh_run<.., HOLD>).
+"""The descent hold of k_trace_split's culling walk (bvh_walk_noovf<.., HOLD>).
 
 After a box step that fewer than `hold` lanes of a wave would follow with another one, while other walking lanes wait
 at a leaf or a miss, the wave leaves the descent loop; the stragglers keep their internal node, do not pop, and take their
@@ -7,7 +7,7 @@ in the same order, so for every hold and every suspend threshold the image and t
 bit for bit, and the box / sphere test counts must equal the hold-0 draw's ("same per-lane visits"). The thresholds
 cover the edges of both checks: hold 1 (a hold no count is below), 2 (the smallest that acts), 64 (every step with a
 waiting lane is held); suspend_below 1 (never suspended: held lanes only ever resume inside one call) and 64 (suspended
-after nearly every pop: held internal nodes go through Q.node and bvh_run's entry).
+after nearly every pop: held internal nodes go through Q.node and bvh_walk_noovf's entry).
 """
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The pop of k_trace_split's culling walk as selects (rt_kernels.hip bvh_run, HRT_POP_ALWAYS).
+"""The pop of k_trace_split's culling walk as selects (rt_kernels.hip bvh_walk_noovf<.., HOLD>, its pop).
 
 After a leaf or a miss a lane pops its next node: the entry below the top of its LDS stack is read by every lane — entry
 0 for an empty stack, its value discarded — and the new node, the new depth and "finished" are selects; a lane the

@@ -1,4 +1,4 @@
-"""The 16-bit walk stack of k_trace_split<LNODES> (rt_kernels.hip bvh_run, the stack entry type; renderer.cpp's gate).
+"""The 16-bit walk stack of k_trace_split<LNODES> (rt_kernels.hip bvh_walk_noovf, the stack entry type SW; renderer.cpp's gate).
 
 With the tree's nodes in LDS a child word is a node index below 192 or LEAF | first << 4 | count with first below 2048:
 15 bits and the leaf bit, so a stack entry is 16 bits — the LDS copy of the nodes holds the words sign-extended from bit

@@ -1,10 +1,13 @@
 // host_capi.cpp — rt_host_* C-ABI over the host scene builders (scene.hpp). Pure CPU.
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
-#include "../../../include/hrt.h"
+#include "../../../include/hrt_testing.h"
 #include "scene.hpp"
+#include "sphere_bvh.hpp"
 
 struct rt_mesh {
     hrt::Mesh mesh;
@@ -105,6 +108,31 @@ int rt_host_compare_ppm(const char* img1, size_t len1, const char* img2, size_t 
                                     tolerance_percent, avg_diff_percent);
     if (code) *code = c;
     return c == 0 ? RT_OK : RT_ERR_COMPARE;
+}
+
+int rt_testing_sphere_bvh_leaves(const float* centers_radii, uint32_t n_slots, uint32_t* leaves, uint32_t leaf_cap,
+                                 int32_t* slots, uint32_t slot_cap, uint32_t counts[4]) {
+    if (!counts || (n_slots && !centers_radii) || (leaf_cap && !leaves) || (slot_cap && !slots)) return RT_ERR_ARG;
+    const hrt::SphereBvh B = hrt::build_sphere_bvh(std::vector<float>(centers_radii, centers_radii + 4 * (size_t)n_slots));
+    std::vector<uint32_t> words;
+    if (B.nodes.empty()) {
+        words.push_back(B.root_word);
+    } else {
+        for (const hrt::SphereBvhNode& n : B.nodes)
+            for (uint32_t w : {n.left, n.right})
+                if (w & hrt::BVH_LEAF_BIT) words.push_back(w);
+    }
+    for (uint32_t& w : words) w &= ~hrt::BVH_LEAF_BIT;
+    std::sort(words.begin(), words.end());  // (first << 4 | count: by first position)
+    counts[0] = (uint32_t)words.size();
+    counts[1] = (uint32_t)B.slot.size();
+    counts[2] = (uint32_t)B.large.size();
+    counts[3] = B.depth;
+    if (leaf_cap < words.size() || slot_cap < B.slot.size() + B.large.size()) return leaf_cap || slot_cap ? RT_ERR_ARG : RT_OK;
+    std::copy(words.begin(), words.end(), leaves);
+    std::copy(B.slot.begin(), B.slot.end(), slots);
+    std::copy(B.large.begin(), B.large.end(), slots + B.slot.size());
+    return RT_OK;
 }
 
 }  // extern "C"

@@ -195,6 +195,9 @@ struct Tally {
     // the mixed kernel's run-to-completion sphere walk (k_trace_split_tris, begin phase): walks entered (waves), and the
     // box / leaf steps run with fewer than DIAG_LOW lanes (waves, lanes)
     uint32_t wentry = 0, wbox_low = 0, lbox_low = 0, wleaf_low = 0, lleaf_low = 0;
+    // k_trace_split's two-pass leaf (-DHRT_LEAFSTAT flushes them): iterations of the first pass (one wait each), runs of
+    // the root pass (leaf steps with a candidate) and its iterations (one root each)
+    uint32_t lpass1 = 0, wpass1 = 0, lrun = 0, wrun = 0, lroot = 0, wroot = 0;
 #endif
 };
 
@@ -202,6 +205,10 @@ struct Tally {
 __device__ __forceinline__ bool first_active_lane() {
     return __lane_id() == (unsigned)(__ffsll((unsigned long long)__ballot(1)) - 1);
 }
+// one more event for the active lanes and, once, for their wave
+#define HRT_TALLY(l, w) (tally.l++, tally.w += first_active_lane() ? 1u : 0u)
+#else
+#define HRT_TALLY(l, w) ((void)0)
 #endif
 
 // (t, slot) lexicographic minimum = the reference's linear scan: strict `t < best` keeps the first slot
@@ -488,7 +495,9 @@ __device__ __forceinline__ void leaf_sphere_test(const KParams& P, const Ray& r,
 // SELECT (k_trace_split): the leaf's spheres in two passes, through buffer loads; else one pass, plain loads.
 // SW: the stack's entry type, uint32_t or (k_trace_split<LNODES> without packets: child words sign-extended from 16
 // bits, `hn` holds them so) int16_t: the push stores the low half, the pop sign-extends it back.
-template <bool SUSPEND, bool SELECT, uint32_t LS, bool COUNT = true, bool HOLD = false, typename SW = uint32_t>
+// PAIR (with SELECT; k_trace_split<LNODES> without packets): the leaf's first pass loads two spheres per wait.
+template <bool SUSPEND, bool SELECT, uint32_t LS, bool COUNT = true, bool HOLD = false, bool PAIR = false,
+          typename SW = uint32_t>
 __device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, BvhQuery& Q, SW* stack, Tally& tally,
                                                uint32_t below, const uint4* __restrict__ hn, uint32_t hold = 0u) {
     constexpr bool S16 = sizeof(SW) == 2;
@@ -603,10 +612,33 @@ __device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, B
                     return float4{v.x, v.y, v.z, v.w};
                 };
                 uint32_t cand = 0u;
-                for (uint32_t o = first * 16u, oe = (first + cnt) * 16u, bit = 1u; o != oe; o += 16u, bit <<= 1) {
-                    if (sphere_candidate(leaf_geo(o), r, a4)) cand |= bit;
+                if constexpr (PAIR) {
+                    // The first pass two spheres at a time: both loads are issued before the wait (the second through
+                    // the load's scalar offset, no address arithmetic), so a leaf costs half the vector-memory round
+                    // trips and half the loop's trips. Three or four per wait spilled at 64 VGPRs.
+                    // The second position of an odd leaf's last pair lies past the lane's count: what it reads — the
+                    // next leaf's first sphere, or zeros past the buffer's end (the resource bounds the read), a
+                    // "candidate" for a ray through the world origin — is excluded by the count after the loop, never
+                    // by its geometry.
+                    for (uint32_t o = first * 16u, oe = (first + cnt) * 16u, bit = 1u; o < oe; o += 32u, bit <<= 2) {
+                        HRT_TALLY(lpass1, wpass1);
+                        const f4v v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o, 0, 0);
+                        const f4v v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)o, 16, 0);
+                        if (sphere_candidate(float4{v0.x, v0.y, v0.z, v0.w}, r, a4)) cand |= bit;
+                        if (sphere_candidate(float4{v1.x, v1.y, v1.z, v1.w}, r, a4)) cand |= bit << 1;
+                    }
+                    cand &= ~(~0u << cnt);
+                } else {
+                    for (uint32_t o = first * 16u, oe = (first + cnt) * 16u, bit = 1u; o != oe; o += 16u, bit <<= 1) {
+                        HRT_TALLY(lpass1, wpass1);
+                        if (sphere_candidate(leaf_geo(o), r, a4)) cand |= bit;
+                    }
                 }
+#ifdef HRT_STAMPS
+                if (cand != 0u) HRT_TALLY(lrun, wrun);
+#endif
                 while (cand != 0u) {
+                    HRT_TALLY(lroot, wroot);
                     const uint32_t o = (first + (uint32_t)__builtin_ctz(cand)) * 16u;
                     cand &= cand - 1u;
                     const float t = candidate_t(leaf_geo(o), r, a4, a2);
@@ -3180,7 +3212,9 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         HRT_LANES(1, have && qs == 1u);
         if (have && qs == 1u) {
             if constexpr (LNODES) {  // (depth <= LNODE_DEPTH = SPLIT_STACK: no overflow)
-                if (bvh_walk_noovf<true, true, 256, COUNT, !PACKET>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
+                // (the leaf's first pass in pairs: not in the stealing kernels, which spilled 2 VGPRs with it)
+                constexpr bool PAIR = !PACKET && !STEAL;
+                if (bvh_walk_noovf<true, true, 256, COUNT, !PACKET, PAIR>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
                     qs = 2u;
             } else {
                 if (bvh_walk_ovf<true, SPLIT_STACK, true, 256, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))
@@ -3250,8 +3284,13 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     HRT_PHASE_FLUSH
 #if defined(HRT_STAMPS) && !defined(HRT_PHASES)
     {
+#ifdef HRT_LEAFSTAT  // (-DHRT_STAMPS -DHRT_LEAFSTAT: the leaf's passes in place of the rounds, shading and walk counts)
+        unsigned long long v[10] = {tally.lbox, tally.wbox, tally.lleaf, tally.wleaf, tally.lpass1, tally.wpass1,
+                                    tally.lrun, tally.wrun, tally.lroot, tally.wroot};
+#else
         unsigned long long v[10] = {tally.lbox, tally.wbox, tally.lleaf, tally.wleaf, tally.rounds, tally.lshade,
                                     tally.wshade, tally.lwalk, tally.wwalk, tally.lentry};
+#endif
 #pragma unroll
         for (int c = 0; c < 10; c++) {
 #pragma unroll

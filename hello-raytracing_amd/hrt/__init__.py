@@ -29,6 +29,29 @@ def check_uniform_guards(n_waves: int, seed: int) -> dict:
     return {h: {c: int(out[i * w + j]) for j, c in enumerate(UGUARD_COLUMNS)} for i, h in enumerate(UGUARD_HELPERS)}
 
 
+def sphere_bvh_leaves(spheres, min_sphere_slots: int = 0) -> dict:
+    """Test-only (include/hrt_testing.h rt_testing_sphere_bvh_leaves, host only): the culling BVH the renderer builds over
+    `spheres` padded with zero slots to min_sphere_slots, as {"leaves": [(first, count), ...] in BVH order, "slots": the
+    slot of every BVH position, "large": the large list's slots, "depth"}."""
+    import ctypes as C
+
+    import numpy as np
+
+    n = max(len(spheres), int(min_sphere_slots))
+    cr = np.zeros((n, 4), dtype=np.float32)
+    if len(spheres):
+        cr[:len(spheres), :3] = spheres["center"]
+        cr[:len(spheres), 3] = spheres["radius"]
+    crp = cr.ctypes.data_as(C.POINTER(C.c_float))
+    counts = (C.c_uint32 * 4)()
+    _lib.check(lib().rt_testing_sphere_bvh_leaves(crp, n, None, 0, None, 0, counts), "rt_testing_sphere_bvh_leaves")
+    words, slots = (C.c_uint32 * max(counts[0], 1))(), (C.c_int32 * max(counts[1] + counts[2], 1))()
+    _lib.check(lib().rt_testing_sphere_bvh_leaves(crp, n, words, len(words), slots, len(slots), counts),
+               "rt_testing_sphere_bvh_leaves")
+    return {"leaves": [(int(w) >> 4, int(w) & 15) for w in words[:counts[0]]], "slots": list(slots[:counts[1]]),
+            "large": list(slots[counts[1]:counts[1] + counts[2]]), "depth": int(counts[3])}
+
+
 __all__ = [
     "HIT_DTYPE", "RT_HIT_FRONT", "RT_HIT_TRIANGLE", "RT_T_MISS",
     "LIB_PATH", "RT_FOLD_AUTO", "RT_FOLD_BUFFER", "RT_FOLD_NEXT", "RT_FOLD_RING", "RT_MODE_MIXED", "RT_SCHEDULE_AUTO", "RT_SCHEDULE_QUEUE", "RT_SCHEDULE_TILES", "RT_MODE_SPHERE", "RT_MODE_TRIS", "RtError", "RtParams", "RtStats", "lib",
@@ -36,4 +59,5 @@ __all__ = [
     "PI", "SPHERE_DTYPE", "TRIANGLE_DTYPE", "Camera", "ComparisonError", "Material", "Mesh", "OrbitCamera", "Renderer",
     "SceneSphere", "SceneTris", "Sphere", "Tree", "Vec3", "compare_ppm_images", "f32", "ppm_from_image",
     "read_asset", "render_ppm", "spheres_array", "device_count", "check_uniform_guards", "UGUARD_COLUMNS", "UGUARD_HELPERS",
+    "sphere_bvh_leaves",
 ]

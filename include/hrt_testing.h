@@ -26,6 +26,15 @@ int rt_testing_set_faults(rt_renderer *r, uint32_t ring_slots_max, uint32_t fail
  *   changes. Stays set until changed; a new renderer starts with the measured default. */
 int rt_testing_set_descent_hold(rt_renderer *r, uint32_t hold);
 
+/* The leaves of the sphere culling BVH the renderer would build over n_slots slots (centers_radii: cx, cy, cz, radius per
+ *   slot, padding slots as zeros). Host only, no device.
+ * leaves: one word per leaf in BVH order, first << 4 | count (first: the leaf's first position in BVH order).
+ * slots: the slot of every BVH position, then the slots of the large list (scanned for every ray, not in the tree).
+ * counts: {leaves, BVH positions, large-list entries, tree depth}; always written. With both capacities 0 only the
+ *   counts are returned; a capacity that is too small otherwise is RT_ERR_ARG. */
+int rt_testing_sphere_bvh_leaves(const float *centers_radii, uint32_t n_slots, uint32_t *leaves, uint32_t leaf_cap,
+                                 int32_t *slots, uint32_t slot_cap, uint32_t counts[4]);
+
 #ifdef __cplusplus
 }
 #endif

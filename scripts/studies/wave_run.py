@@ -1,6 +1,7 @@
 """Driver of scripts/studies/wave_sim.cpp (round-7 study: the wave-lockstep model of k_trace_split).
 
 usage: python scripts/studies/wave_run.py [--config c3] [--waves 40] [--jobs 6] [--suspend 24] [--hold 0 8 12 ...]
+       python scripts/studies/wave_run.py --hold 12 --cand-hold 0/0 8/1 12/1 16/2 24/4 64/2   
        python scripts/studies/wave_run.py --calibrate      (suspend_below 24, hold 0 against the GPU's diagnostic counters)
 Builds the simulator with g++ into a temporary directory, writes the scene beside it and prints the simulator's counts
 per setting; with several settings, a table of the wave's box steps, lanes per box step and the modelled issue cost.
@@ -31,10 +32,13 @@ ap.add_argument("--jobs", type=int, default=6)
 ap.add_argument("--job-frames", type=int, default=32)
 ap.add_argument("--suspend", type=int, nargs="+", default=[24])
 ap.add_argument("--hold", type=int, nargs="+", default=[0])
+ap.add_argument("--cand-hold", nargs="+", default=["0/0"], metavar="CHOLD/CWAIT",
+                help="the candidate hold priced in round 10 (0/0 = none): the root pass waits for CHOLD lanes with a "
+                     "candidate, at most CWAIT iterations")
 ap.add_argument("--calibrate", action="store_true")
 a = ap.parse_args()
 if a.calibrate:
-    a.suspend, a.hold = [24], [0]
+    a.suspend, a.hold, a.cand_hold = [24], [0], ["0/0"]
 
 sd = scenes.CONFIGS[a.config]()
 assert sd.bvh is None, "the model is of the sphere program"
@@ -50,18 +54,23 @@ with tempfile.TemporaryDirectory() as tmp:
     scene.write_bytes(cam + struct.pack("<I", len(sph) // 48) + sph)
     for sb in a.suspend:
         for hold in a.hold:
-            out = subprocess.run([str(exe), str(scene), str(sd.width), str(sd.height), str(sd.bounces or 50), str(a.waves),
-                                  str(a.jobs), str(sb), str(hold), str(a.job_frames)], capture_output=True, text=True,
-                                 check=True).stdout
-            print(out.split("\nJSON ", 1)[0] + "\n")
-            rows.append(json.loads(out.split("\nJSON ", 1)[1]))
+            for ch in a.cand_hold:
+                chold, cwait = ch.split("/")
+                out = subprocess.run([str(exe), str(scene), str(sd.width), str(sd.height), str(sd.bounces or 50),
+                                      str(a.waves), str(a.jobs), str(sb), str(hold), str(a.job_frames), chold, cwait],
+                                     capture_output=True, text=True, check=True).stdout
+                print(out.split("\nJSON ", 1)[0] + "\n")
+                rows.append(json.loads(out.split("\nJSON ", 1)[1]))
 
 if len(rows) > 1:
     base = rows[0]
-    print("suspend_below hold  wave box steps / 64 q  lanes / box step  issue cost / query  vs the first row")
+    print("suspend_below hold chold/cwait  wave box steps / 64 q  lanes / box step  root runs / 64 q  lanes / run  "
+          "issue cost / query  vs the first row")
     for r in rows:
-        print(f"{r['suspend_below']:13d} {r['hold']:4d} {r['wave_box_per_64q']:22.2f} {r['box_lanes']:17.1f} "
-              f"{r['cost_per_query']:19.2f} {100.0 * (r['cost_per_query'] / base['cost_per_query'] - 1.0):+15.1f} %")
+        ch = f"{r['chold']}/{r['cwait']}"
+        print(f"{r['suspend_below']:13d} {r['hold']:4d} {ch:>11s} {r['wave_box_per_64q']:22.2f} {r['box_lanes']:17.1f} "
+              f"{r['root_runs_per_64q']:16.2f} {r['root_lanes']:11.1f} "
+              f"{r['cost_per_query']:19.3f} {100.0 * (r['cost_per_query'] / base['cost_per_query'] - 1.0):+15.1f} %")
 
 if a.calibrate:
     line = next(ln for ln in DIAG_LOG.read_text().splitlines() if ln.startswith("suspend_below 24"))

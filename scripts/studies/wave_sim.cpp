@@ -12,6 +12,9 @@
 //           that fewer than min(hold, lanes that entered the iteration) lanes would follow with another one; the
 //           stragglers keep their node, skip the pop, and step in the next iteration). After the pop the walk is
 //           suspended when fewer than `suspend_below` lanes still walk.
+//           `chold` > 0 is the candidate hold priced in round 10 (never built): a lane whose leaf gave it a candidate keeps
+//           its leaf word and its candidates and skips the pop; the wave runs the root pass only once at least `chold`
+//           lanes of the call hold a candidate, or every lane of the call does, or a lane has waited `cwait` iterations.
 //   shade   lanes whose walk has finished: the hit (the oracle's closest_sphere), then scatter or the sample's end.
 // Paths are the oracle's (make_ray / closest_sphere / scatter, oracle/rt_oracle.c); the tree is build_sphere_bvh's with
 // its f32 boxes unpadded, as in packet_sim.cpp — a model of the kernel's padded fp16 test, not the test itself.
@@ -57,6 +60,7 @@ struct Lane {
     int sp = 0;
     float bt = 0, a = 0;
     v3 inv;
+    uint32_t cand = 0, cwaited = 0;  // the leaf's candidates not yet resolved (bit j: sphere first + j), iterations waited
 };
 
 struct Counts {  // w*: wave events, l*: lanes taking part
@@ -65,12 +69,13 @@ struct Counts {  // w*: wave events, l*: lanes taking part
     double wbegin = 0, lbegin = 0;
     double wcall = 0, lcall = 0, wwalk = 0, lwalk = 0;
     double wbox = 0, lbox = 0, wleaf = 0, lleaf = 0, leaf_maxcnt = 0, leaf_maxcand = 0, whold = 0, lheld = 0;
+    double wroot = 0, lroot = 0, wchold = 0, lcheld = 0;  // root-pass runs and their lanes (leaf_maxcand: their iterations)
     double wshade = 0, lshade = 0;
 };
 
 struct Sim {
     o_scene sc;
-    uint32_t W, H, B, suspend_below, hold, job_frames;
+    uint32_t W, H, B, suspend_below, hold, job_frames, chold = 0, cwait = 0;
     Counts C;
 
     ray_t primary(uint32_t x, uint32_t y, uint32_t time, uint32_t& s) {  // fs_main prologue (oracle sample_pixel)
@@ -115,20 +120,33 @@ struct Sim {
         return !miss && !(L.node & hrt::BVH_LEAF_BIT);
     }
 
-    void leaf_step(Lane& L, uint32_t& cnt_out, uint32_t& cand_out) {
-        const uint32_t first = (L.node >> 4) & 0x07FFFFFFu, cnt = L.node & 15u;
-        uint32_t cand = 0;
+    // the leaf's first pass (sphere_candidate of every sphere: the lane's candidates) and its second (their roots)
+    static void leaf_terms(const Lane& L, uint32_t j, float& b, float& disc) {
+        const float* g = GS + 4 * (((L.node >> 4) & 0x07FFFFFFu) + j);
+        v3 oc = V(L.ray.o.x - g[0], L.ray.o.y - g[1], L.ray.o.z - g[2]);
+        b = 2.0f * dot3(oc, L.ray.d);
+        disc = fmaf(b, b, -((4.0f * L.a) * (dot3(oc, oc) - g[3])));
+    }
+    uint32_t leaf_pass1(Lane& L) {
+        const uint32_t cnt = L.node & 15u;
+        L.cand = 0;
         for (uint32_t j = 0; j < cnt; j++) {
-            const float* g = GS + 4 * (first + j);
-            v3 oc = V(L.ray.o.x - g[0], L.ray.o.y - g[1], L.ray.o.z - g[2]);
-            float b = 2.0f * dot3(oc, L.ray.d), c = dot3(oc, oc) - g[3];
-            float disc = fmaf(b, b, -((4.0f * L.a) * c));
-            if (!(disc >= 0.0f && b <= 0.0f)) continue;  // sphere_candidate
-            cand++;
+            float b, disc;
+            leaf_terms(L, j, b, disc);
+            if (disc >= 0.0f && b <= 0.0f) L.cand |= 1u << j;  // sphere_candidate
+        }
+        return cnt;
+    }
+    uint32_t leaf_roots(Lane& L) {
+        const uint32_t n = (uint32_t)__builtin_popcount(L.cand);
+        for (uint32_t j = 0; L.cand != 0; j++, L.cand >>= 1) {
+            if (!(L.cand & 1u)) continue;
+            float b, disc;
+            leaf_terms(L, j, b, disc);
             float t = (-b - sqrtf(disc)) / (2.0f * L.a);
             if (t > 0.0f && t < L.bt) L.bt = t;
         }
-        cnt_out = cnt, cand_out = cand;
+        return n;
     }
 
     // bvh_walk_noovf for the lanes of `w` (qs == 1), in lockstep
@@ -159,18 +177,29 @@ struct Sim {
                 }
                 D.swap(D2);
             }
-            uint32_t nl = 0, mc = 0, mk = 0;
+            // (a lane held with a candidate kept its leaf word only: it takes the first pass again)
+            uint32_t nl = 0, mc = 0, mk = 0, nc = 0, waited = 0;
             for (int l : act) {
                 if (held[l] || missed[l] || !(lanes[l].node & hrt::BVH_LEAF_BIT)) continue;
-                uint32_t cnt, cand;
-                leaf_step(lanes[l], cnt, cand);
-                nl++, mc = std::max(mc, cnt), mk = std::max(mk, cand);
+                if (lanes[l].cand == 0) lanes[l].cwaited = 0;
+                nl++, mc = std::max(mc, leaf_pass1(lanes[l]));
+                if (lanes[l].cand != 0) nc++, waited = std::max(waited, lanes[l].cwaited);
             }
-            if (nl) C.wleaf++, C.lleaf += nl, C.leaf_maxcnt += mc, C.leaf_maxcand += mk;
+            if (nl) C.wleaf++, C.lleaf += nl, C.leaf_maxcnt += mc;
+            std::vector<char> cheld(64);
+            if (nc && (nc >= chold || nc == act.size() || waited >= cwait)) {
+                for (int l : act)
+                    if (lanes[l].cand != 0) mk = std::max(mk, leaf_roots(lanes[l]));
+                C.wroot++, C.lroot += nc, C.leaf_maxcand += mk;
+            } else if (nc) {  // the candidate hold
+                for (int l : act)
+                    if (lanes[l].cand != 0) cheld[l] = 1, lanes[l].cwaited++;
+                C.wchold++, C.lcheld += nc;
+            }
             std::vector<int> next;
             for (int l : act) {
                 Lane& L = lanes[l];
-                if (!held[l]) {
+                if (!held[l] && !cheld[l]) {
                     if (L.sp == 0) {
                         L.qs = 2;
                         continue;
@@ -288,7 +317,8 @@ struct Sim {
 
 int main(int argc, char** argv) {
     if (argc < 9) {
-        fprintf(stderr, "usage: wave_sim scene.bin W H bounces waves jobs_per_wave suspend_below hold [job_frames = 32]\n");
+        fprintf(stderr, "usage: wave_sim scene.bin W H bounces waves jobs_per_wave suspend_below hold [job_frames = 32] "
+                        "[chold = 0] [cwait = 0]\n");
         return 2;
     }
     FILE* f = fopen(argv[1], "rb");
@@ -304,6 +334,7 @@ int main(int argc, char** argv) {
     const uint32_t waves = atoi(argv[5]), jobs = atoi(argv[6]);
     S.suspend_below = std::max(atoi(argv[7]), 1), S.hold = atoi(argv[8]);
     S.job_frames = argc > 9 ? atoi(argv[9]) : 32;
+    S.chold = argc > 10 ? atoi(argv[10]) : 0, S.cwait = argc > 11 ? atoi(argv[11]) : 0;
     std::vector<float> cr(4 * nsl);
     for (uint32_t i = 0; i < nsl; i++) {
         cr[4 * i] = sph[i].center[0], cr[4 * i + 1] = sph[i].center[1], cr[4 * i + 2] = sph[i].center[2];
@@ -339,6 +370,10 @@ int main(int argc, char** argv) {
            "step)  shade %.2f  begin %.2f;  holds per 64 queries %.3f (lanes held %.2f)\n",
            C.lwalk / C.wwalk, C.lbox / C.wbox, C.lleaf / C.wleaf, C.leaf_maxcnt / C.wleaf, C.leaf_maxcand / C.wleaf,
            C.lshade / C.wshade, C.lbegin / std::max(C.wbegin, 1.0), C.whold / q64, C.lheld / std::max(C.whold, 1.0));
+    printf("root pass per 64 queries:  runs %.2f  iterations %.2f  lanes per run %.1f;  candidate hold %u / %u: holds %.3f "
+           "(lanes held %.2f)\n",
+           C.wroot / q64, C.leaf_maxcand / q64, C.lroot / std::max(C.wroot, 1.0), S.chold, S.cwait, C.wchold / q64,
+           C.lcheld / std::max(C.wchold, 1.0));
     // issue-slot price per query (rough weights, see the head of this file)
     const double c_refill = 340.0 * C.wblock + 40.0 * C.wdeal, c_begin = 130.0 * C.wbegin, c_shade = 260.0 * C.wshade;
     const double c_walk = 51.0 * C.wbox + 50.0 * C.wcall + 15.0 * C.leaf_maxcnt + 45.0 * C.leaf_maxcand + 12.0 * C.wwalk;
@@ -347,8 +382,10 @@ int main(int argc, char** argv) {
            c_begin / tot, c_walk / tot, c_shade / tot);
     printf("JSON {\"suspend_below\": %u, \"hold\": %u, \"queries\": %.0f, \"walk_lanes\": %.3f, \"box_lanes\": %.3f, "
            "\"leaf_lanes\": %.3f, \"shade_lanes\": %.3f, \"wave_box_per_64q\": %.4f, \"lane_box_per_q\": %.4f, \"cost_per_query\": %.4f, "
-           "\"share_refill\": %.4f, \"share_begin\": %.4f, \"share_walk\": %.4f, \"share_shade\": %.4f}\n",
+           "\"share_refill\": %.4f, \"share_begin\": %.4f, \"share_walk\": %.4f, \"share_shade\": %.4f, \"chold\": %u, "
+           "\"cwait\": %u, \"root_runs_per_64q\": %.4f, \"root_iterations_per_64q\": %.4f, \"root_lanes\": %.3f}\n",
            S.suspend_below, S.hold, q, C.lwalk / C.wwalk, C.lbox / C.wbox, C.lleaf / C.wleaf, C.lshade / C.wshade, C.wbox / q64,
-           C.lbox / q, tot / q, c_refill / tot, c_begin / tot, c_walk / tot, c_shade / tot);
+           C.lbox / q, tot / q, c_refill / tot, c_begin / tot, c_walk / tot, c_shade / tot, S.chold, S.cwait, C.wroot / q64,
+           C.leaf_maxcand / q64, C.lroot / std::max(C.wroot, 1.0));
     return 0;
 }

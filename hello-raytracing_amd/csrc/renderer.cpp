@@ -26,6 +26,8 @@ hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, h
 hipError_t hrt_launch_accumulate(const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_cast(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs, uint32_t n,
                            void* hits, hipStream_t stream);
+hipError_t hrt_launch_occluded(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs,
+                               const float* tmax, uint32_t n, void* occluded, hipStream_t stream);
 hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
                                    hipStream_t stream);
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
@@ -1336,6 +1338,24 @@ int rt_cast_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev, 
     if (rc) return rc;
     const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
     HIP_TRY(hrt_launch_cast(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev, n, hits_dev, r->stream));
+    return RT_OK;
+}
+
+int rt_occluded(rt_renderer* r, const void* origins_dev, const void* dirs_dev, const void* tmax_dev, uint32_t n,
+                void* occluded_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_occluded: null");
+    if (n == 0) return RT_OK;
+    if (!origins_dev || !dirs_dev || !occluded_dev) return fail(RT_ERR_ARG, "rt_occluded: null buffer");
+    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u || (uintptr_t)tmax_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_occluded: origins, directions and tmax must be 4-byte aligned");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
+    HIP_TRY(hrt_launch_occluded(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev,
+                                (const float*)tmax_dev, n, occluded_dev, r->stream));
     return RT_OK;
 }
 

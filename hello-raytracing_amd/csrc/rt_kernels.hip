@@ -62,7 +62,9 @@ struct Hit {
 // the closest root with t > 0 && t < best (first slot wins ties), or -1. Skipping b >= 0 is exact:
 // then -b - sqrt(disc) <= 0, so t <= 0 (or NaN) and the reference rejects it too.
 // (PP: a KParams pointer, generic or the kernarg segment's constant one: kargs())
-template <typename PP>
+// ANY (any_hit): the lane leaves the loop at its first accepted slot — some slot with 0 < t < the starting `best`, not
+// the closest. The scan assumes nothing about the starting value: it only ever compares `t < best`.
+template <bool ANY = false, typename PP>
 __device__ __forceinline__ int scan_spheres_p(PP P, const Ray& r, float& best) {
     const float a = dot(r.d, r.d);
     const float a4 = 4.0f * a;
@@ -83,11 +85,15 @@ __device__ __forceinline__ int scan_spheres_p(PP P, const Ray& r, float& best) {
                 bi = (int)i;
             }
         }
+        if constexpr (ANY) {
+            if (bi >= 0) break;
+        }
     }
     return bi;
 }
+template <bool ANY = false>
 __device__ __forceinline__ int scan_spheres(const KParams& P, const Ray& r, float& best) {
-    return scan_spheres_p(&P, r, best);
+    return scan_spheres_p<ANY>(&P, r, best);
 }
 
 
@@ -113,6 +119,9 @@ __device__ __forceinline__ float exact_sphere_t(const KParams& P, const Ray& r, 
 // beside the mixed deferred-scan kernels' 32 KB of LDS at 5 workgroups per CU)
 constexpr int CAND_CAP = 14;
 
+// ANY (any_hit): pass 2 stops at the lane's first accepted candidate, and the overflow fallback is scan_spheres<ANY>.
+// Pass 1 does not read `best`, and pass 2 and the fallback only compare `t < best`: any starting value is taken exactly.
+template <bool ANY = false>
 __device__ __forceinline__ int scan_spheres_deferred(const KParams& P, const Ray& r, float& best,
                                                      uint16_t* __restrict__ lds_list) {
     const float a = dot(r.d, r.d);
@@ -145,7 +154,7 @@ __device__ __forceinline__ int scan_spheres_deferred(const KParams& P, const Ray
             cnt++;
         }
     }
-    if (cnt > (uint32_t)CAND_CAP) return scan_spheres(P, r, best);  // overflow: exact full scan
+    if (cnt > (uint32_t)CAND_CAP) return scan_spheres<ANY>(P, r, best);  // overflow: exact full scan
 
     int bi = -1;
     float bt = best;
@@ -160,6 +169,9 @@ __device__ __forceinline__ int scan_spheres_deferred(const KParams& P, const Ray
                 bt = t;
                 bi = (int)i;
             }
+        }
+        if constexpr (ANY) {
+            if (bi >= 0) break;
         }
     }
     best = bt;
@@ -697,7 +709,11 @@ __device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, B
 // SO (Q from bvh_begin<.., SO>): box_hit_so; else padded_box_hit on the decoded node.
 // SELECT (k_trace_split): select-form child order, +1 % on C3; the three-way branch keeps k_trace's mixed program
 // (C5) free of spills (the select form spilled 12 VGPRs there, -1.5 %); with it the leaves' spheres as leaf_sphere_test<FAST>.
-template <bool SUSPEND, int STACK, bool SELECT, uint32_t LS, bool SO, bool COUNT = true>
+// ANY (any_hit; Q from a bvh_begin started at the query's tmax that accepted no large sphere, bc < 0): the walk ends for
+// the lane at the first sphere a leaf test accepts. Exact for "some sphere with 0 < t < tmax": a smaller starting bt is
+// the state a closest-hit walk is in after a hit at that t, except that no slot is held, and with bc < 0 the leaf test
+// refuses an equal t (beats()); the boxes culled by bt hold only spheres with t > bt, as in that walk.
+template <bool SUSPEND, int STACK, bool SELECT, uint32_t LS, bool SO, bool COUNT = true, bool ANY = false>
 __device__ __forceinline__ bool bvh_walk_ovf(const KParams& P, const Ray& r, BvhQuery& Q, uint32_t* stack, Tally& tally,
                                              uint32_t below, const uint4* __restrict__ hn) {
     const Slab S = Q.S;
@@ -774,8 +790,19 @@ __device__ __forceinline__ bool bvh_walk_ovf(const KParams& P, const Ray& r, Bvh
             }
 #endif
             const uint32_t first = (node >> 4) & 0x07FFFFFFu, cnt = node & 15u;
-            for (uint32_t j = 0; j < cnt; j++) leaf_sphere_test<SELECT>(P, r, a4, a2, first + j, bt, bc);
+            for (uint32_t j = 0; j < cnt; j++) {
+                leaf_sphere_test<SELECT>(P, r, a4, a2, first + j, bt, bc);
+                if constexpr (ANY) {
+                    if (bc >= 0) break;
+                }
+            }
             if constexpr (COUNT) tally.spheres += cnt;
+        }
+        if constexpr (ANY) {
+            if (bc >= 0) {
+                finished = 1u;
+                break;
+            }
         }
         if (sp == 0) {
             finished = 1u;
@@ -795,17 +822,18 @@ __device__ __forceinline__ bool bvh_walk_ovf(const KParams& P, const Ray& r, Bvh
 }
 
 // KA: the fallback scan reads its constants through kargs() (k_trace_split: no SGPRs held for the rare path)
-template <bool KA = false>
+// ANY: that scan as scan_spheres<ANY> (it starts from the caller's `best`, the query's own starting value, not Q.bt)
+template <bool KA = false, bool ANY = false>
 __device__ __forceinline__ int bvh_end(const KParams& P, const Ray& r, const BvhQuery& Q, float& best,
                                        Tally& tally) {
     if (Q.full_scan != 0u) {
         if constexpr (KA) {
             const KPtr K = kargs();
             tally.spheres += K->nslots;
-            return scan_spheres_p(K, r, best);
+            return scan_spheres_p<ANY>(K, r, best);
         }
         tally.spheres += P.nslots;
-        return scan_spheres(P, r, best);
+        return scan_spheres<ANY>(P, r, best);
     }
     best = Q.bt;
     return Q.bc >= 0 ? bvh_slot_of(P, Q.bc) : -1;
@@ -813,16 +841,21 @@ __device__ __forceinline__ int bvh_end(const KParams& P, const Ray& r, const Bvh
 
 // The whole query, walked to completion. NOOVF (the caller's tree is no deeper than the stack; with SO):
 // bvh_walk_noovf, else bvh_walk_ovf with its STACK-entry bound.
-template <int STACK = BVH_STACK, uint32_t LS = 256, bool KA = false, bool NOOVF = false, bool SO = false>
+// ANY (any_hit, `best` = the query's tmax): a lane whose large list already holds an accepted sphere skips the walk, and
+// the walk and the fallback scan stop at their first accepted sphere; the slot returned is some occluder's, not the closest's.
+template <int STACK = BVH_STACK, uint32_t LS = 256, bool KA = false, bool NOOVF = false, bool SO = false, bool ANY = false>
 __device__ __forceinline__ int scan_spheres_bvh(const KParams& P, const Ray& r, float& best, uint32_t* stack,
                                                 Tally& tally) {
     static_assert(!NOOVF || SO, "bvh_walk_noovf is sign-ordered");
+    static_assert(!ANY || !NOOVF, "the any-hit exit is bvh_walk_ovf's");
     BvhQuery Q;
     if (bvh_begin<false, KA, SO>(P, r, best, Q, tally)) {
-        if constexpr (NOOVF) bvh_walk_noovf<false, false, LS>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
+        if constexpr (ANY) {
+            if (Q.bc < 0) bvh_walk_ovf<false, STACK, false, LS, SO, true, true>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
+        } else if constexpr (NOOVF) bvh_walk_noovf<false, false, LS>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
         else bvh_walk_ovf<false, STACK, false, LS, SO>(P, r, Q, stack, tally, 0u, P.bvh_hnodes);
     }
-    return bvh_end<KA>(P, r, Q, best, tally);
+    return bvh_end<KA, ANY>(P, r, Q, best, tally);
 }
 
 // (p - c) / radius, exact: the host's correctly rounded 1 / radius and two residual corrections
@@ -1171,8 +1204,11 @@ constexpr uint32_t PAIR_BIT = 0x80000000u;
 // triangles.)
 typedef __attribute__((address_space(3))) uint32_t lds_u32;  // 32-bit LDS addressing for the list
 
+// ANY (any_hit; W.best = the query's tmax): a lane that holds an accepted triangle after a flush stops walking (and
+// leaves the flush at that triangle). The path does not depend on hits, so the walk is cut short, never rerouted: every
+// step up to the exit falls where the closest-hit walk's does, the 600-step cap included.
 template <bool SUSPEND, uint32_t HT = 0, uint32_t LS = 256, uint32_t CAP = TRI_BATCH, bool TBUF = false, bool SO = false,
-          bool FULL = false>
+          bool FULL = false, bool ANY = false>
 __device__ __forceinline__ bool heap_run(const KParams& P, const Ray& r, HeapWalk& W, Tally& tally, uint32_t* cand_g,
                                          uint32_t below, const float* __restrict__ top = nullptr) {
     // the list's LDS byte address (32-bit arithmetic): entry k at c0 + k * 4 LS
@@ -1238,8 +1274,14 @@ __device__ __forceinline__ bool heap_run(const KParams& P, const Ray& r, HeapWal
             const uint32_t j = e & ~PAIR_BIT;
             tri_test<TBUF>(P, r, j, best, bj);
             if (e & PAIR_BIT) tri_test<TBUF>(P, r, j + 1u, best, bj);
+            if constexpr (ANY) {
+                if (bj >= 0) break;
+            }
         }
         nc = 0u;
+        if constexpr (ANY) {
+            if (bj >= 0) walking = 0u;
+        }
         if (walking == 0u) break;
         if constexpr (SUSPEND) {
             if ((uint32_t)__popcll(__ballot(1)) < below) break;
@@ -1273,6 +1315,10 @@ constexpr int TRI_STACK = 24;
 
 // (the SAH tree's constants are read through kargs() where they are used, not held in SGPRs across the persistent
 // loop: the mixed kernels with this walk spilled 2-10 SGPRs otherwise)
+// ANY (any_hit; best = the query's tmax, bj = -1): the walk, and the overflow fallback's loop, end at the first accepted
+// triangle. With no triangle held an equal t is refused (`bj >= 0` in the tie rule), so t == tmax does not occlude; the
+// boxes culled by `best` hold only triangles the closest-hit walk started at FLT_MAX_REF would find beyond it.
+template <bool ANY = false>
 __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, float& best, int& bj, Tally& tally,
                                          uint32_t* stack) {
     const KPtr P = kargs();
@@ -1320,6 +1366,9 @@ __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, flo
                     best = t;
                     bj = (int)j;
                 }
+                if constexpr (ANY) {
+                    if (bj >= 0) return;
+                }
             }
         }
         if (sp == 0) break;
@@ -1331,6 +1380,9 @@ __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, flo
             if (t >= 1e-4f && (t < best || (t == best && bj >= 0 && (int)j < bj))) {
                 best = t;
                 bj = (int)j;
+            }
+            if constexpr (ANY) {
+                if (bj >= 0) return;
             }
         }
         tally.tris += P->m;
@@ -1370,6 +1422,56 @@ __device__ __forceinline__ bool closest_hit(const KParams& P, const Ray& r, Hit&
         return true;
     }
     h.t = FLT_MAX_REF;
+    return false;
+}
+
+// The occlusion query (k_occluded, rt_occluded): true exactly when closest_hit would return a hit with t < tmax (f32
+// comparison) for the same ray. closest_hit's t is the minimum over everything its walks accept, so "that minimum is
+// below tmax" is "some accepted candidate is below tmax": every walk starts at best = tmax instead of FLT_MAX_REF and
+// the lane is done at its first accepted candidate (the ANY forms above, each with the reason it is exact). No hit
+// record is built and the test counts are dropped.
+//   - tmax is clamped to FLT_MAX_REF first (every accepted t is below it: +inf and FLT_MAX mean "any hit at all");
+//     NaN and tmax <= 0 (either zero) occlude nothing, since every accepted t is > 0: no walk runs.
+//   - mixed program: spheres first; an occluded lane skips the triangle walk, the others walk the triangles with
+//     best = tmax. closest_hit starts its triangle walk at the sphere's t, >= tmax for these lanes; the reference walk's
+//     path is the same for any start (no best-t test on nodes), and the SAH walk only culls what lies beyond its start.
+// The reference heap walk's deferred list holds ANY_TRI_BATCH entries here: the exit is checked after a flush, so a
+// shorter list finds the hit after fewer node steps at the price of more flushes. Measured at 4 / 8 / 16 on Suzanne, the
+// capped dragon and C4: 4 wins only where most rays hit early and loses up to 23 % where none can stop,
+// 16 the reverse; 8 is never the slowest.
+constexpr uint32_t ANY_TRI_BATCH = 8;
+static_assert(ANY_TRI_BATCH <= TRI_BATCH, "lane_lists sizes the triangle list for TRI_BATCH entries");
+
+template <int MODE, int SCAN, bool TSAH = false>
+__device__ __forceinline__ bool any_hit(const KParams& P, const Ray& r, float tmax, void* lds, uint32_t* tri_cand,
+                                        uint32_t* tri_stack) {
+    if (!(tmax > 0.0f)) return false;
+    float best = fmin_ieee(tmax, FLT_MAX_REF);
+    Tally tally;
+    if (MODE != MODE_TRIS) {
+        int bi;
+        if constexpr (SCAN == SCAN_BVH) {
+            bi = scan_spheres_bvh<BVH_STACK, 256, TSAH, false, false, true>(P, r, best, (uint32_t*)lds, tally);
+        } else if constexpr (SCAN == SCAN_DEFER) {
+            bi = scan_spheres_deferred<true>(P, r, best, (uint16_t*)lds);
+        } else {
+            bi = scan_spheres<true>(P, r, best);
+        }
+        // (a sphere scan that accepted something has lowered `best` below tmax; the lane is done, so that is not read)
+        if (bi >= 0) return true;
+    }
+    if (MODE != MODE_SPHERE) {
+        int bj = -1;
+        if constexpr (TSAH) {
+            walk_sah<true>(P, r, best, bj, tally, tri_stack);
+        } else {
+            HeapWalk W;
+            heap_begin(r, best, W);
+            heap_run<false, 0, 256, ANY_TRI_BATCH, false, false, false, true>(P, r, W, tally, tri_cand, 0u);
+            bj = W.bj;
+        }
+        return bj >= 0;
+    }
     return false;
 }
 
@@ -2506,6 +2608,26 @@ __global__ __launch_bounds__(256) void k_cast_rays(const KParams P, const float*
     }
     hits[(size_t)i * 2u] = lo;
     hits[(size_t)i * 2u + 1u] = hi;
+}
+
+// Occlusion queries for the caller's rays (rt_occluded): k_cast_rays' shape — one ray per lane, the same per-lane lists,
+// the scene only — with a per-ray bound (tmax null: FLT_MAX_REF, any hit at all) and one byte per ray, 1 when any_hit
+// finds an occluder below the bound. Each lane stores its own byte: exactly n bytes are written, at any alignment.
+// Lanes that finish early leave their loops; a wave ends with its last lane.
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) void k_occluded(const KParams P, const float* __restrict__ origins,
+                                                  const float* __restrict__ dirs, const float* __restrict__ tmax, uint32_t n,
+                                                  uint8_t* __restrict__ occluded) {
+    const LaneLists lists = lane_lists<MODE, SCAN>();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float* const po = origins + (size_t)i * 3u;
+    const float* const pd = dirs + (size_t)i * 3u;
+    Ray ray;
+    ray.o = mk(po[0], po[1], po[2]);
+    ray.d = mk(pd[0], pd[1], pd[2]);
+    const float tm = tmax != nullptr ? tmax[i] : FLT_MAX_REF;
+    occluded[i] = any_hit<MODE, SCAN, TSAH>(P, ray, tm, lists.sphere, lists.tri, lists.tri) ? (uint8_t)1 : (uint8_t)0;
 }
 
 // The primary rays of one frame (rt_primary_rays): lane i is pixel (i % W, local row i / W) and stores the origin and
@@ -4303,6 +4425,42 @@ hipError_t hrt_launch_cast(int mode, int variant, const KParams& P, const float*
     default:
         if (P.tri_bvh) launch_cast_mode<MODE_MIXED, true>(variant, P, origins, dirs, n, h, grid, block, stream);
         else launch_cast_mode<MODE_MIXED, false>(variant, P, origins, dirs, n, h, grid, block, stream);
+        break;
+    }
+    return hipGetLastError();
+}
+
+// Host-side launcher of rt_occluded: k_cast_rays' instantiation set and grid.
+template <int MODE, bool TSAH>
+static void launch_occluded_mode(int variant, const KParams& P, const float* origins, const float* dirs, const float* tmax,
+                                 uint32_t n, uint8_t* occ, dim3 grid, dim3 block, hipStream_t stream) {
+    if constexpr (MODE == MODE_TRIS) {
+        hipLaunchKernelGGL((k_occluded<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
+    } else {
+        if (variant == SCAN_SIMPLE)
+            hipLaunchKernelGGL((k_occluded<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
+        else if (variant == SCAN_DEFER)
+            hipLaunchKernelGGL((k_occluded<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
+        else
+            hipLaunchKernelGGL((k_occluded<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
+    }
+}
+
+hipError_t hrt_launch_occluded(int mode, int variant, const KParams& P, const float* origins, const float* dirs,
+                               const float* tmax, uint32_t n, void* occluded, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    dim3 block(256);
+    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
+    uint8_t* const o = (uint8_t*)occluded;
+    switch (mode) {
+    case MODE_SPHERE: launch_occluded_mode<MODE_SPHERE, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream); break;
+    case MODE_TRIS:
+        if (P.tri_bvh) launch_occluded_mode<MODE_TRIS, true>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
+        else launch_occluded_mode<MODE_TRIS, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
+        break;
+    default:
+        if (P.tri_bvh) launch_occluded_mode<MODE_MIXED, true>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
+        else launch_occluded_mode<MODE_MIXED, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
         break;
     }
     return hipGetLastError();

@@ -110,6 +110,7 @@ SIGNATURES = {
     "rt_draw": (C.c_int, [_P]),
     "rt_draw_frames": (C.c_int, [_P, _U32, _U32, _U32]),
     "rt_cast_rays": (C.c_int, [_P, _P, _P, _U32, _P]),
+    "rt_occluded": (C.c_int, [_P, _P, _P, _P, _U32, _P]),
     "rt_primary_rays": (C.c_int, [_P, _U32, _P, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),

@@ -430,6 +430,45 @@ class Renderer:
         return {"t": f[:, 0].clone(), "prim": hits[:, 1].clone(), "normal": f[:, 2:5].clone(),
                 "flags": hits[:, 5].clone(), "material": hits[:, 6].clone()}
 
+    def occluded(self, origins, dirs, tmax=None):
+        """rt_occluded: for each ray, whether cast_rays would return a hit with t < tmax (an f32 comparison; a hit at
+        exactly tmax does not occlude). origins and dirs as cast_rays; tmax is None (any hit at all), a Python float
+        for every ray, or an (N,) float32 numpy array or tensor on the renderer's device. A segment from a to b is
+        origins = a, dirs = b - a, tmax = 1. Returns a torch.bool tensor (N,) on the renderer's device. Synchronises
+        torch's current stream before the call and the renderer after it."""
+        import torch
+
+        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError(f"occluded: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
+        n = int(o.shape[0])
+        if n >= 1 << 32:
+            raise ValueError("occluded: at most 2^32 - 1 rays per call")
+        dev = self._torch_device()
+        t = None
+        if tmax is not None:
+            if isinstance(tmax, (int, float)):
+                t = torch.full((n,), float(tmax), dtype=torch.float32, device=dev)
+            else:
+                t = tmax
+                if not torch.is_tensor(t):
+                    t = np.asarray(t)
+                    if t.dtype != np.float32:
+                        raise ValueError(f"occluded: tmax must be float32, got {t.dtype}")
+                    t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+                if t.dtype != torch.float32 or tuple(t.shape) != (n,):
+                    raise ValueError(f"occluded: tmax must be ({n},) float32, got {tuple(t.shape)} {t.dtype}")
+                if t.device != dev:
+                    raise ValueError(f"occluded: tmax is on {t.device}, the renderer draws on {dev}")
+                t = t.contiguous()
+        out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_occluded(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                C.c_void_p(t.data_ptr()) if t is not None else None, n, C.c_void_p(out.data_ptr())),
+              "occluded")
+        self.synchronize()
+        return out != 0
+
     def primary_rays(self, time: int):
         """rt_primary_rays: (origins, dirs), each (local_rows, width, 3) float32 on the renderer's device — the rays the
         frame drawn at `time` traces first for each of this renderer's pixels."""

@@ -260,6 +260,25 @@ typedef struct rt_hit {             /* 32 B */
  * steal and cost-order knobs do not. n = 0 returns RT_OK and launches nothing; n > 0 with a null pointer is RT_ERR_ARG. A
  * scene state in which a draw fails gives the same status here; no camera is needed. */
 int rt_cast_rays(rt_renderer *r, const void *origins_dev, const void *dirs_dev, uint32_t n, void *hits_dev);
+/* The occlusion query: is anything in the way before distance tmax? n rays -> n bytes, 1 = occluded, 0 = not.
+ * origins_dev / dirs_dev as rt_cast_rays (n x 3 f32, packed, 4-byte aligned); tmax_dev: n f32 (4-byte aligned) or NULL =
+ * RT_T_MISS for every ray ("any hit at all"); occluded_dev: n bytes, no alignment. Device memory on the renderer's GPU,
+ * asynchronous on the renderer's stream, as rt_cast_rays.
+ * The whole contract: for the same renderer state and the same ray, byte i is 1 exactly when rt_cast_rays would return a
+ * hit (prim >= 0) with t < tmax[i], as an f32 comparison. So everything rt_cast_rays documents carries over — the sphere
+ * program's unnormalised d (tmax in units of |d|), triangles from t >= 1e-4, the reference walk's 600-step cap (a
+ * triangle the capped walk never reaches does not occlude), zero padding slots counted as spheres, rt_params.variant /
+ * tri_bvh / min_sphere_slots — and a hit at exactly t == tmax does not occlude. A NaN tmax, or any tmax <= 0 including
+ * -0, gives 0; a tmax above RT_T_MISS (+inf, FLT_MAX) behaves as RT_T_MISS. Only the values 0 and 1 are ever written,
+ * and exactly n bytes are written.
+ * A segment query from a to b is o = a, d = b - a, tmax = 1. In the triangle and mixed programs the triangle test's
+ * absolute |det| >= 1e-4 makes the result depend on |d| (a short d can fall under it), as it does for rt_cast_rays.
+ * The walks start at tmax instead of RT_T_MISS and stop at the first occluder, so a short ray skips most of the scene;
+ * no hit record is built. n = 0 returns RT_OK and launches nothing; n > 0 with a null origins, dirs or occluded pointer,
+ * or a misaligned f32 buffer, is RT_ERR_ARG. A scene state in which a draw fails gives the same status here; no camera
+ * is needed. Like the calls beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_occluded(rt_renderer *r, const void *origins_dev, const void *dirs_dev, const void *tmax_dev, uint32_t n,
+                void *occluded_dev);
 /* The primary rays of the frame drawn at `time` (rt_set_time): for local row k and column x, ray k * width + x is the one
  * fs_main traces for that pixel — antialiasing jitter, lens offset and, in the triangle and mixed programs, the
  * normalised direction included — as 3 f32 origin and 3 f32 direction, packed like rt_cast_rays' inputs (device memory,
@@ -340,8 +359,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
  * / rt_get_stats copy this header's sizes. A caller built against another header checks *version == RT_ABI_VERSION (or
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
-                             5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream came
-                             later without a new version (no struct changed): detect them by their symbols */
+                             5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
+                             rt_occluded, came later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

@@ -28,8 +28,11 @@ hipError_t hrt_launch_cast(int mode, int variant, const hrt_dev::KParams& P, con
                            void* hits, hipStream_t stream);
 hipError_t hrt_launch_occluded(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs,
                                const float* tmax, uint32_t n, void* occluded, hipStream_t stream);
+hipError_t hrt_launch_trace_rays(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs,
+                                 const uint32_t* rng, uint32_t seed, uint32_t n, uint32_t R, float* radiance, uint32_t* queries,
+                                 hipStream_t stream);
 hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
-                                   hipStream_t stream);
+                                   uint32_t* state, hipStream_t stream);
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -221,6 +224,7 @@ struct rt_renderer {
     uint32_t last_schedule = 0;
     uint32_t last_suspend = 0;
     uint32_t test_ring_slots_max = 0, test_fail_alloc_above_mb = 0;  // hrt_testing.h fault injection
+    uint32_t trace_rays_per_lane = 0;  // k_radiance_rays' R forced (hrt_testing.h); 0 = the rule (trace_rays_per_lane())
     uint32_t descent_hold = DESCENT_HOLD_DEFAULT;  // k_trace_split<LNODES>'s descent hold (hrt_testing.h moves it)
     uint32_t ring_slots = 0;  // fold-ring slots of the last sample-queue draw
     uint32_t ring_tiles = 0, ring_nchunks = 0;  // (diagnostics: HRT_RING_DUMP)
@@ -1287,6 +1291,13 @@ int rt_testing_set_descent_hold(rt_renderer* r, uint32_t hold) {
     return RT_OK;
 }
 
+int rt_testing_set_trace_rays_per_lane(rt_renderer* r, uint32_t rays_per_lane) {
+    if (rays_per_lane > 64) return fail(RT_ERR_ARG, "rt_testing_set_trace_rays_per_lane: rays_per_lane must be 0..64");
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_trace_rays_per_lane: null");
+    r->trace_rays_per_lane = rays_per_lane;
+    return RT_OK;
+}
+
 int rt_set_time(rt_renderer* r, uint32_t time) {
     if (!r) return fail(RT_ERR_ARG, "rt_set_time: null");
     r->time = time;
@@ -1359,6 +1370,43 @@ int rt_occluded(rt_renderer* r, const void* origins_dev, const void* dirs_dev, c
     return RT_OK;
 }
 
+// Rays per lane of k_radiance_rays (R; a wave owns 64 R consecutive rays): the largest of 4, 2, 1 that still leaves 48
+// waves per compute unit — two full rounds at the kernel's 6 waves per SIMD. A lane with several rays takes the next one
+// when a path ends instead of idling behind the wave's longest, but each doubling halves the waves and pulls the lanes
+// of a wave apart (their rays are 64 apart, and no longer on the same bounce). Measured on C3's primary rays with 50
+// bounces, in pixel order / permuted, as ms per call (DESIGN.md §7c Radiance queries): 0.92 M rays R = 1: 0.56 / 0.72,
+// R = 2 (28 waves per CU): 0.70 / 0.68; 2.07 M rays R = 1: 0.93 / 1.30, R = 2 (63 per CU): 0.86 / 1.09, R = 4 (32):
+// 0.88 / 1.03; 3.69 M rays R = 2: 1.23 / 1.69, R = 4 (56): 1.21 / 1.50; 8.29 M rays R = 4: 2.28 / 2.96, R = 8 (63):
+// 2.34 / 2.69 — 8 never won on both orders.
+static uint32_t trace_rays_per_lane(const rt_renderer* r, uint32_t n) {
+    if (r->trace_rays_per_lane) return r->trace_rays_per_lane;
+    const uint64_t waves_wanted = 48ull * std::max(r->cus, 1u);
+    uint32_t R = 4;
+    while (R > 1 && (uint64_t)n < 64ull * R * waves_wanted) R >>= 1;
+    return R;
+}
+
+int rt_trace_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev, const void* rng_dev, uint32_t seed, uint32_t n,
+                  void* radiance_dev, void* queries_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_trace_rays: null");
+    if (n == 0) return RT_OK;
+    if (!origins_dev || !dirs_dev || !radiance_dev) return fail(RT_ERR_ARG, "rt_trace_rays: null buffer");
+    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u || (uintptr_t)rng_dev % 4u || (uintptr_t)radiance_dev % 4u ||
+        (uintptr_t)queries_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_trace_rays: origins, directions, states, radiance and queries must be 4-byte aligned");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    P.bounces = r->params.bounces;
+    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
+    HIP_TRY(hrt_launch_trace_rays(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev,
+                                  (const uint32_t*)rng_dev, seed, n, trace_rays_per_lane(r, n), (float*)radiance_dev,
+                                  (uint32_t*)queries_dev, r->stream));
+    return RT_OK;
+}
+
 int rt_primary_rays(rt_renderer* r, uint32_t time, void* origins_dev, void* dirs_dev, size_t n_rays) {
     if (!r) return fail(RT_ERR_ARG, "rt_primary_rays: null");
     if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before rt_primary_rays");
@@ -1373,7 +1421,24 @@ int rt_primary_rays(rt_renderer* r, uint32_t time, void* origins_dev, void* dirs
     hrt_dev::KParams P{};
     int rc = scene_params(r, P);
     if (rc) return rc;
-    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, (float*)origins_dev, (float*)dirs_dev, r->stream));
+    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, (float*)origins_dev, (float*)dirs_dev, nullptr, r->stream));
+    return RT_OK;
+}
+
+int rt_primary_rng(rt_renderer* r, uint32_t time, void* rng_dev, size_t n_rays) {
+    if (!r) return fail(RT_ERR_ARG, "rt_primary_rng: null");
+    if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before rt_primary_rng");
+    if (n_rays != (size_t)r->local_rows() * r->width)
+        return fail(RT_ERR_ARG, "rt_primary_rng: n_rays must be local_rows x width");
+    if (n_rays == 0) return RT_OK;
+    if (!rng_dev) return fail(RT_ERR_ARG, "rt_primary_rng: null buffer");
+    if ((uintptr_t)rng_dev % 4u) return fail(RT_ERR_ARG, "rt_primary_rng: the states must be 4-byte aligned");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, nullptr, nullptr, (uint32_t*)rng_dev, r->stream));
     return RT_OK;
 }
 

@@ -2630,18 +2630,99 @@ __global__ __launch_bounds__(256) void k_occluded(const KParams P, const float* 
     occluded[i] = any_hit<MODE, SCAN, TSAH>(P, ray, tm, lists.sphere, lists.tri, lists.tri) ? (uint8_t)1 : (uint8_t)0;
 }
 
+// Path-traced radiance for the caller's rays (rt_trace_rays): trace() of the renderer's program — k_render's bounce loop
+// (closest_hit, scatter<MODE>, the attenuation and sky expressions, the 0.0f + c of fs_main's mix at weight 1) with the
+// ray, its RNG state and the output slot taken from the caller. rng null: state (i + 1) * seed. Reads the scene only: no
+// image, no counters (the Tally is dropped; the lane's query count is kept for `queries` alone).
+// A wave owns the 64 R consecutive rays from (its index) * 64 R and lane l traces base + 64 k + l for k = 0 .. R - 1 one
+// after another inside one loop — k_render's structure with "the next frame of my pixel" replaced by "my next ray of the
+// chunk" — so a lane whose path ends early loads its next ray while the others walk on, and lanes idle only at the end
+// of a chunk. R = 1 is one ray per lane. Grid: ceil(ceil(n / 64 R) / 4) workgroups of 256 (lane_lists: 256 lanes).
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) void k_radiance_rays(const KParams P, const float* __restrict__ origins,
+                                                    const float* __restrict__ dirs, const uint32_t* __restrict__ rng,
+                                                    uint32_t seed, uint32_t n, uint32_t R, float* __restrict__ radiance,
+                                                    uint32_t* __restrict__ queries_out) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const LaneLists lists = lane_lists<MODE, SCAN>();
+    void* const lds_list = lists.sphere;
+    uint32_t* const tri_cand = lists.tri;
+    uint32_t* const tri_stack = lists.tri;
+    Tally tally;
+    const unsigned long long chunk = 64ull * R;
+    const unsigned long long base = ((unsigned long long)blockIdx.x * 4u + wave) * chunk;
+    const unsigned long long end = base + chunk < (unsigned long long)n ? base + chunk : (unsigned long long)n;
+    unsigned long long i = base + lane;
+
+    // Path state of the lane's current ray.
+    Ray ray;
+    f3 att = mk(1.0f, 1.0f, 1.0f);
+    float sky_t = 0.0f;
+    uint32_t s = 0, bounce = 0, queries = 0;
+    if (i < end) {
+        const float* const po = origins + i * 3u;
+        const float* const pd = dirs + i * 3u;
+        ray.o = mk(po[0], po[1], po[2]);
+        ray.d = mk(pd[0], pd[1], pd[2]);
+        s = rng != nullptr ? rng[i] : ((uint32_t)i + 1u) * seed;
+        sky_t = ray.d.y * 0.5f + 0.5f;
+    }
+    while (i < end) {
+        bool done = true;
+        if (bounce < P.bounces) {
+            Hit h;
+            const bool hit = closest_hit<MODE, SCAN, TSAH>(P, ray, h, lds_list, tally, tri_cand, tri_stack);
+            queries++;
+            if (hit) {
+                scatter<MODE>(P, s, ray, h);
+                att = att * mk(h.ar * 0.7f, h.ag * 0.7f, h.ab * 0.7f);
+                bounce++;
+                done = bounce >= P.bounces;
+            }
+        }
+        if (done) {
+            // trace() epilogue (:241-242), then fs_main's `0.0 + trace(ray)` (:264-271 at frame_count 0, weight 1).
+            const float u = 1.0f - sky_t;
+            const f3 sky = mk(0.54f * u + 0.54f * sky_t, 0.86f * u + 0.7f * sky_t, 0.92f * u + 0.98f * sky_t);
+            const f3 c = att * sky;
+            float* const out = radiance + i * 3u;
+            out[0] = 0.0f + c.x;
+            out[1] = 0.0f + c.y;
+            out[2] = 0.0f + c.z;
+            if (queries_out != nullptr) queries_out[i] = queries;
+            i += 64u;
+            if (i < end) {
+                const float* const po = origins + i * 3u;
+                const float* const pd = dirs + i * 3u;
+                ray.o = mk(po[0], po[1], po[2]);
+                ray.d = mk(pd[0], pd[1], pd[2]);
+                s = rng != nullptr ? rng[i] : ((uint32_t)i + 1u) * seed;
+                sky_t = ray.d.y * 0.5f + 0.5f;
+                att = mk(1.0f, 1.0f, 1.0f);
+                bounce = 0;
+                queries = 0;
+            }
+        }
+    }
+}
+
 // The primary rays of one frame (rt_primary_rays): lane i is pixel (i % W, local row i / W) and stores the origin and
 // direction primary_ray<MODE> gives k_render for that pixel in the frame drawn at `time` (jitter, lens offset and, in the
-// triangle and mixed programs, the normalised direction included), packed 3 x f32. Grid: ceil(nrows W / 256) x 256.
+// triangle and mixed programs, the normalised direction included), packed 3 x f32. With `state` (rt_primary_rng) it stores
+// the RNG state primary_ray leaves behind instead, one u32 per pixel. Grid: ceil(nrows W / 256) x 256.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_primary_rays(const KParams P, uint32_t time, float* __restrict__ origins,
-                                                      float* __restrict__ dirs) {
+                                                      float* __restrict__ dirs, uint32_t* __restrict__ state) {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= (size_t)P.nrows * P.W) return;
     const uint32_t kr = (uint32_t)(i / P.W), x = (uint32_t)(i - (size_t)kr * P.W);
     const uint32_t y = global_row(P.row0, P.row_block, P.row_stride, kr);
     uint32_t s = 0;
     const Ray ray = primary_ray<MODE>(&kargs()->cam, x, y, time, s);
+    if (state != nullptr) {  // (rt_primary_rng: the state alone)
+        state[i] = s;
+        return;
+    }
     float* const po = origins + i * 3u;
     float* const pd = dirs + i * 3u;
     po[0] = ray.o.x; po[1] = ray.o.y; po[2] = ray.o.z;
@@ -4466,15 +4547,56 @@ hipError_t hrt_launch_occluded(int mode, int variant, const KParams& P, const fl
     return hipGetLastError();
 }
 
-hipError_t hrt_launch_primary_rays(int mode, const KParams& P, uint32_t time, float* origins, float* dirs, hipStream_t stream) {
+// Host-side launcher of rt_trace_rays: k_cast_rays' instantiation set; a wave per 64 R rays (k_radiance_rays).
+using RadianceKernel = void (*)(const KParams, const float*, const float*, const uint32_t*, uint32_t, uint32_t, uint32_t,
+                                float*, uint32_t*);
+template <int MODE, bool TSAH>
+static RadianceKernel radiance_kernel(int variant) {
+    if constexpr (MODE == MODE_TRIS) {
+        return k_radiance_rays<MODE, SCAN_SIMPLE, TSAH>;
+    } else {
+        if (variant == SCAN_SIMPLE) return k_radiance_rays<MODE, SCAN_SIMPLE, TSAH>;
+        if (variant == SCAN_DEFER) return k_radiance_rays<MODE, SCAN_DEFER, TSAH>;
+        return k_radiance_rays<MODE, SCAN_BVH, TSAH>;
+    }
+}
+
+// R: rays per lane (>= 1, chosen by the host: renderer.cpp trace_rays_per_lane).
+hipError_t hrt_launch_trace_rays(int mode, int variant, const KParams& P, const float* origins, const float* dirs,
+                                 const uint32_t* rng, uint32_t seed, uint32_t n, uint32_t R, float* radiance, uint32_t* queries,
+                                 hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (R == 0) R = 1;
+    const unsigned long long waves = ((unsigned long long)n + 64ull * R - 1u) / (64ull * R);
+    dim3 block(256);
+    dim3 grid((uint32_t)((waves + 3u) / 4u));
+    RadianceKernel k;
+    switch (mode) {
+    case MODE_SPHERE: k = radiance_kernel<MODE_SPHERE, false>(variant); break;
+    case MODE_TRIS: k = P.tri_bvh ? radiance_kernel<MODE_TRIS, true>(variant) : radiance_kernel<MODE_TRIS, false>(variant); break;
+    default: k = P.tri_bvh ? radiance_kernel<MODE_MIXED, true>(variant) : radiance_kernel<MODE_MIXED, false>(variant); break;
+    }
+    hipLaunchKernelGGL(k, grid, block, 0, stream, P, origins, dirs, rng, seed, n, R, radiance, queries);
+    return hipGetLastError();
+}
+
+// state null: the rays (rt_primary_rays); state given: the RNG state after primary_ray alone (rt_primary_rng).
+hipError_t hrt_launch_primary_rays(int mode, const KParams& P, uint32_t time, float* origins, float* dirs, uint32_t* state,
+                                   hipStream_t stream) {
     const unsigned long long n = (unsigned long long)P.nrows * P.W;
     if (n == 0) return hipSuccess;
     dim3 block(256);
     dim3 grid((uint32_t)((n + 255u) / 256u));
     switch (mode) {
-    case MODE_SPHERE: hipLaunchKernelGGL((k_primary_rays<MODE_SPHERE>), grid, block, 0, stream, P, time, origins, dirs); break;
-    case MODE_TRIS: hipLaunchKernelGGL((k_primary_rays<MODE_TRIS>), grid, block, 0, stream, P, time, origins, dirs); break;
-    default: hipLaunchKernelGGL((k_primary_rays<MODE_MIXED>), grid, block, 0, stream, P, time, origins, dirs); break;
+    case MODE_SPHERE:
+        hipLaunchKernelGGL((k_primary_rays<MODE_SPHERE>), grid, block, 0, stream, P, time, origins, dirs, state);
+        break;
+    case MODE_TRIS:
+        hipLaunchKernelGGL((k_primary_rays<MODE_TRIS>), grid, block, 0, stream, P, time, origins, dirs, state);
+        break;
+    default:
+        hipLaunchKernelGGL((k_primary_rays<MODE_MIXED>), grid, block, 0, stream, P, time, origins, dirs, state);
+        break;
     }
     return hipGetLastError();
 }

@@ -112,6 +112,8 @@ SIGNATURES = {
     "rt_cast_rays": (C.c_int, [_P, _P, _P, _U32, _P]),
     "rt_occluded": (C.c_int, [_P, _P, _P, _P, _U32, _P]),
     "rt_primary_rays": (C.c_int, [_P, _U32, _P, _P, C.c_size_t]),
+    "rt_trace_rays": (C.c_int, [_P, _P, _P, _P, _U32, _U32, _P, _P]),
+    "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),
     "rt_write_image": (C.c_int, [_P, _PF, C.c_size_t]),
@@ -156,6 +158,7 @@ SIGNATURES = {
 TESTING_SIGNATURES = {
     "rt_testing_set_faults": (C.c_int, [_P, _U32, _U32]),
     "rt_testing_set_descent_hold": (C.c_int, [_P, _U32]),
+    "rt_testing_set_trace_rays_per_lane": (C.c_int, [_P, _U32]),
     "rt_testing_sphere_bvh_leaves": (C.c_int, [C.POINTER(C.c_float), _U32, C.POINTER(_U32), _U32,
                                                C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
 }

@@ -491,6 +491,74 @@ class Renderer:
         hit = self.cast_rays(o.view(-1, 3), d.view(-1, 3))
         return {k: v.view(*o.shape[:2], *v.shape[1:]) for k, v in hit.items()}
 
+    def trace_rays(self, origins, dirs, rng=None, seed: int = 0, want_queries: bool = False):
+        """rt_trace_rays: the path-traced radiance of each ray, trace() of the renderer's program with rt_params.bounces
+        bounces. origins and dirs as cast_rays; rng is None (ray i starts from the state (i + 1) * seed mod 2^32) or the
+        (N,) int32 / uint32 states, a numpy array or a tensor on the renderer's device (int32 holds the same 32 bits).
+        Returns (N, 3) float32 radiance on the renderer's device and, with want_queries, also the (N,) int32 number of
+        closest-hit queries each path took. Synchronises torch's current stream before the call and the renderer after
+        it."""
+        import torch
+
+        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError(f"trace_rays: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
+        n = int(o.shape[0])
+        if n >= 1 << 32:
+            raise ValueError("trace_rays: at most 2^32 - 1 rays per call")
+        dev = self._torch_device()
+        s = None
+        if rng is not None:
+            s = rng
+            if not torch.is_tensor(s):
+                s = np.asarray(s)
+                if s.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+                    raise ValueError(f"trace_rays: rng must be int32 or uint32, got {s.dtype}")
+                s = torch.from_numpy(np.ascontiguousarray(s).view(np.int32)).to(dev)
+            if s.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(s.shape) != (n,):
+                raise ValueError(f"trace_rays: rng must be ({n},) int32, got {tuple(s.shape)} {s.dtype}")
+            if s.device != dev:
+                raise ValueError(f"trace_rays: rng is on {s.device}, the renderer draws on {dev}")
+            s = s.contiguous()
+        rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        q = torch.empty((n,), dtype=torch.int32, device=dev) if want_queries else None
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_trace_rays(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                  C.c_void_p(s.data_ptr()) if s is not None else None, int(seed) & 0xFFFFFFFF, n,
+                                  C.c_void_p(rad.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None),
+              "trace_rays")
+        self.synchronize()
+        return (rad, q) if want_queries else rad
+
+    def primary_rng(self, time: int):
+        """rt_primary_rng: (local_rows, width) int32 on the renderer's device — the RNG state fs_main holds after
+        make_ray for each of this renderer's pixels in the frame drawn at `time` (the 32 bits of the u32 state)."""
+        import torch
+
+        dev = self._torch_device()
+        shape = (self.local_rows, self.width)
+        s = torch.empty(shape, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_primary_rng(self._h, int(time) & 0xFFFFFFFF, C.c_void_p(s.data_ptr()), shape[0] * shape[1]),
+              "primary_rng")
+        self.synchronize()
+        return s
+
+    def trace_frame(self, time: int, want_queries: bool = False):
+        """The radiance of each pixel sample of the frame drawn at `time`: trace_rays on primary_rays and primary_rng,
+        shaped (local_rows, width, 3) — bit for bit the image a one-frame draw at that time leaves from frame count 0.
+        With want_queries also the (local_rows, width) queries. The counterpart of first_hit."""
+        o, d = self.primary_rays(time)
+        s = self.primary_rng(time)
+        out = self.trace_rays(o.view(-1, 3), d.view(-1, 3), rng=s.view(-1), want_queries=want_queries)
+        if want_queries:
+            return out[0].view(*o.shape), out[1].view(*o.shape[:2])
+        return out.view(*o.shape)
+
+    def set_trace_rays_per_lane(self, rays_per_lane: int) -> None:
+        """Test-only: k_radiance_rays' rays per lane, 0 = the host's rule (include/hrt_testing.h)."""
+        check(lib().rt_testing_set_trace_rays_per_lane(self._h, rays_per_lane), "testing_set_trace_rays_per_lane")
+
     def stats(self) -> RtStats:
         s = RtStats()
         check(lib().rt_get_stats(self._h, C.byref(s)), "get_stats")

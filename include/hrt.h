@@ -285,6 +285,33 @@ int rt_occluded(rt_renderer *r, const void *origins_dev, const void *dirs_dev, c
  * asynchronous on the renderer's stream). Needs a camera (RT_ERR_STATE otherwise, as drawing does); n_rays must equal
  * local_rows x width (RT_ERR_ARG otherwise). rt_cast_rays on them gives the first hit behind each pixel sample. */
 int rt_primary_rays(rt_renderer *r, uint32_t time, void *origins_dev, void *dirs_dev, size_t n_rays);
+/* The radiance query: n rays -> n radiances, the colour fs_main would mix into a pixel whose primary ray this is
+ * (0.0 + trace(ray)): the whole multi-bounce path of the renderer's program for rays the caller makes.
+ * origins_dev / dirs_dev as rt_cast_rays (n x 3 f32, packed, 4-byte aligned). rng_dev: n u32 (4-byte aligned), entry i
+ * the RNG state ray i's path starts from — the `s` that scatter advances — or NULL = the state s_i = (i + 1) * seed in
+ * u32 arithmetic (by analogy with the reference's (x * H + y) * time); seed is ignored when rng_dev is given, and rng_dev
+ * is only read. radiance_dev: n x 3 f32, packed, 4-byte aligned; exactly 12 n bytes are written. queries_dev: n u32
+ * (4-byte aligned) or NULL; it receives the number of closest-hit queries ray i's path took, 0 .. rt_params.bounces, and
+ * exactly 4 n bytes are written when it is given. Device memory on the renderer's GPU, asynchronous on the renderer's
+ * stream, as rt_cast_rays.
+ * The path is exactly trace() of the renderer's program: each bounce is the query rt_cast_rays documents, then scatter,
+ * then attenuation by albedo * 0.7, up to rt_params.bounces times; the sky term is taken from the GIVEN ray's d.y. In the
+ * sphere program d is not normalised, so the caller's |d| enters the sky blend exactly as it would in trace().
+ * Everything rt_cast_rays documents carries over — the sphere program's unnormalised d, triangles from t >= 1e-4 and the
+ * |det| >= 1e-4 threshold, the reference walk's 600-step cap unless tri_bvh = 1, zero padding slots counted as spheres —
+ * and rt_params.variant, tri_bvh, min_sphere_slots and bounces apply as in a tiles draw. bounces = 0 gives the sky colour
+ * and 0 queries. So with the rays of rt_primary_rays and the states of rt_primary_rng for one `time`, the result is bit
+ * for bit the image a one-frame draw at that time leaves from frame count 0, and the queries sum to its ray count.
+ * n = 0 returns RT_OK and launches nothing; n > 0 with a null origins, dirs or radiance pointer, or a misaligned buffer,
+ * is RT_ERR_ARG. A scene state in which a draw fails gives the same status here; no camera is needed. Like the calls
+ * beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_trace_rays(rt_renderer *r, const void *origins_dev, const void *dirs_dev, const void *rng_dev, uint32_t seed,
+                  uint32_t n, void *radiance_dev, void *queries_dev);
+/* The RNG state fs_main holds after make_ray for each pixel of the frame drawn at `time` (the companion of
+ * rt_primary_rays: same pixel order, same row partition): n_rays u32, 4-byte aligned device memory, asynchronous on the
+ * renderer's stream. Needs a camera (RT_ERR_STATE otherwise); n_rays must equal local_rows x width (RT_ERR_ARG
+ * otherwise). */
+int rt_primary_rng(rt_renderer *r, uint32_t time, void *rng_dev, size_t n_rays);
 /* The renderer's HIP stream (a hipStream_t, created non-blocking; owned by the renderer, valid until rt_destroy): for a
  * caller that orders its own streams against the asynchronous calls above with events instead of rt_synchronize, or
  * times them (scripts/bench_cast.py). */
@@ -360,7 +387,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
-                             rt_occluded, came later without a new version (no struct changed): detect them by their symbols */
+                             rt_occluded, then rt_trace_rays / rt_primary_rng, came later without a new version (no struct
+                             changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

@@ -26,6 +26,12 @@ int rt_testing_set_faults(rt_renderer *r, uint32_t ring_slots_max, uint32_t fail
  *   changes. Stays set until changed; a new renderer starts with the measured default. */
 int rt_testing_set_descent_hold(rt_renderer *r, uint32_t hold);
 
+/* rays_per_lane: R of rt_trace_rays' kernel (k_radiance_rays): a wave owns 64 R consecutive rays and each lane traces
+ *   R of them one after another. 0..64 (RT_ERR_ARG above), 0 = the host's rule by batch size. Every value gives the
+ *   same radiance and queries; only the speed changes (scripts/bench_trace_rays.py sweeps it). Stays set until changed;
+ *   a new renderer starts with 0. */
+int rt_testing_set_trace_rays_per_lane(rt_renderer *r, uint32_t rays_per_lane);
+
 /* The leaves of the sphere culling BVH the renderer would build over n_slots slots (centers_radii: cx, cy, cz, radius per
  *   slot, padding slots as zeros). Host only, no device.
  * leaves: one word per leaf in BVH order, first << 4 | count (first: the leaf's first position in BVH order).

@@ -31,6 +31,8 @@ hipError_t hrt_launch_occluded(int mode, int variant, const hrt_dev::KParams& P,
 hipError_t hrt_launch_trace_rays(int mode, int variant, const hrt_dev::KParams& P, const float* origins, const float* dirs,
                                  const uint32_t* rng, uint32_t seed, uint32_t n, uint32_t R, float* radiance, uint32_t* queries,
                                  hipStream_t stream);
+hipError_t hrt_launch_bounce(int mode, int variant, const hrt_dev::KParams& P, const hrt_dev::BounceIO& io, uint32_t n,
+                             hipStream_t stream);
 hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
                                    uint32_t* state, hipStream_t stream);
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
@@ -1404,6 +1406,46 @@ int rt_trace_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev,
     HIP_TRY(hrt_launch_trace_rays(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev,
                                   (const uint32_t*)rng_dev, seed, n, trace_rays_per_lane(r, n), (float*)radiance_dev,
                                   (uint32_t*)queries_dev, r->stream));
+    return RT_OK;
+}
+
+// One path step in the caller's buffers (include/hrt.h rt_bounce): *count_out is zeroed on the stream, then k_bounce_rays.
+int rt_bounce_rays(rt_renderer* r, const rt_bounce* io, uint32_t n) {
+    if (!r) return fail(RT_ERR_ARG, "rt_bounce_rays: null");
+    if (n == 0) return RT_OK;
+    if (!io) return fail(RT_ERR_ARG, "rt_bounce_rays: null io");
+    if (!io->origins_dev || !io->dirs_dev || !io->rng_dev) return fail(RT_ERR_ARG, "rt_bounce_rays: null buffer");
+    if (io->reserved != 0) return fail(RT_ERR_ARG, "rt_bounce_rays: reserved must be 0");
+    if (io->index_out_dev && !io->count_out_dev) return fail(RT_ERR_ARG, "rt_bounce_rays: index_out needs count_out");
+    if (io->count_out_dev && io->count_out_dev == io->count_in_dev)
+        return fail(RT_ERR_ARG, "rt_bounce_rays: count_out must not be count_in");
+    if (!io->index_in_dev && n > io->paths) return fail(RT_ERR_ARG, "rt_bounce_rays: n exceeds paths without index_in");
+    if ((uintptr_t)io->hits_dev % 16u) return fail(RT_ERR_ARG, "rt_bounce_rays: hits must be 16-byte aligned");
+    if ((uintptr_t)io->origins_dev % 4u || (uintptr_t)io->dirs_dev % 4u || (uintptr_t)io->rng_dev % 4u ||
+        (uintptr_t)io->throughput_dev % 4u || (uintptr_t)io->queries_dev % 4u || (uintptr_t)io->index_in_dev % 4u ||
+        (uintptr_t)io->count_in_dev % 4u || (uintptr_t)io->index_out_dev % 4u || (uintptr_t)io->count_out_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_bounce_rays: every buffer but hits must be 4-byte aligned");
+    static_assert(sizeof(rt_bounce) == 88, "rt_bounce: ten pointers and two words (hrt/_lib.py RtBounce)");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
+    hrt_dev::BounceIO B{};
+    B.origins = (float*)io->origins_dev;
+    B.dirs = (float*)io->dirs_dev;
+    B.rng = (uint32_t*)io->rng_dev;
+    B.throughput = (float*)io->throughput_dev;
+    B.queries = (uint32_t*)io->queries_dev;
+    B.hits = io->hits_dev;
+    B.index_in = (const uint32_t*)io->index_in_dev;
+    B.count_in = (const uint32_t*)io->count_in_dev;
+    B.index_out = (uint32_t*)io->index_out_dev;
+    B.count_out = (uint32_t*)io->count_out_dev;
+    B.paths = io->paths;
+    if (B.count_out) HIP_TRY(hipMemsetAsync(B.count_out, 0, sizeof(uint32_t), r->stream));
+    HIP_TRY(hrt_launch_bounce(r->mode, variant, P, B, n, r->stream));
     return RT_OK;
 }
 

@@ -219,6 +219,21 @@ struct KParams {
     uint32_t bq_pad[3];
 };
 
+// The caller's buffers of one path step (rt_bounce_rays, include/hrt.h rt_bounce), typed: k_bounce_rays' second argument.
+struct BounceIO {
+    float* origins;
+    float* dirs;
+    uint32_t* rng;
+    float* throughput;         // or null
+    uint32_t* queries;         // or null
+    void* hits;                // or null; 32-B records, 16-byte aligned
+    const uint32_t* index_in;  // or null: path i is entry i
+    const uint32_t* count_in;  // or null: all n entries
+    uint32_t* index_out;       // or null
+    uint32_t* count_out;       // or null (given whenever index_out is)
+    uint32_t paths;
+};
+
 // KParams in the kernarg segment (constant address space: scalar loads), as a pointer the compiler cannot
 // trace back to the kernel's entry, so every use is a fresh s_load (K$) instead of a live SGPR.
 typedef const __attribute__((address_space(4))) KParams* KPtr;

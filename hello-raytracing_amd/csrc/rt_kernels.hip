@@ -2706,6 +2706,76 @@ __global__ __launch_bounds__(256) void k_radiance_rays(const KParams P, const fl
     }
 }
 
+// One path step for the caller's paths (rt_bounce_rays): one iteration of trace()'s loop — k_radiance_rays' loop body
+// (closest_hit, scatter<MODE>, the attenuation expression) with the ray, the RNG state and the throughput read from and
+// written back to the caller's arrays, and k_cast_rays' record of the ray before the scatter. k_cast_rays' shape: one entry
+// per lane, ceil(n / 256) workgroups of 256, the scene only (the Tally is dropped).
+// Entry i is path j = index_in ? index_in[i] : i. A lane past min(n, *count_in) or with j >= paths is not `active`: it
+// reads and writes nothing and stays out of the query, but it is NOT returned early — every lane of the wave reaches the
+// ballot below, so the leader is elected among whatever lanes hit (lane 0 may be inactive or a miss).
+// Compaction, wave-aggregated: the wave's hitting lanes are __ballot(hit); the first of them takes popcount slots of
+// index_out with one relaxed agent-scope atomic on count_out, the base is broadcast with readfirstlane, and each hitting
+// lane stores j at base + (hitting lanes below it). A wave with no hit issues no atomic. With count_out alone the paths
+// are only counted.
+template <int MODE, int SCAN, bool TSAH = false>
+__global__ __launch_bounds__(256) void k_bounce_rays(const KParams P, const BounceIO io, uint32_t n) {
+    const LaneLists lists = lane_lists<MODE, SCAN>();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t live = n;
+    if (io.count_in != nullptr) live = min(n, *io.count_in);
+    bool active = i < live;
+    uint32_t j = i;
+    if (active && io.index_in != nullptr) j = io.index_in[i];
+    active = active && j < io.paths;
+    bool hit = false;
+    if (active) {
+        float* const po = io.origins + (size_t)j * 3u;
+        float* const pd = io.dirs + (size_t)j * 3u;
+        Ray ray;
+        ray.o = mk(po[0], po[1], po[2]);
+        ray.d = mk(pd[0], pd[1], pd[2]);
+        Tally tally;
+        Hit h;
+        int tri = -1;
+        hit = closest_hit<MODE, SCAN, TSAH>(P, ray, h, lists.sphere, tally, lists.tri, lists.tri, &tri);
+        if (io.queries != nullptr) io.queries[j] += 1u;
+        if (io.hits != nullptr) {  // (k_cast_rays' record, of the ray before the scatter)
+            uint4 lo = {__float_as_uint(FLT_MAX_REF), 0xFFFFFFFFu, 0u, 0u}, hi = {0u, 0u, 0u, 0u};  // miss: t, prim -1, zeros
+            if (hit) {
+                const bool sphere = MODE == MODE_SPHERE || (MODE == MODE_MIXED && (h.id & 4u) != 0u);
+                lo = uint4{__float_as_uint(h.t), sphere ? h.id >> 3 : (uint32_t)tri, __float_as_uint(h.n.x), __float_as_uint(h.n.y)};
+                hi = uint4{__float_as_uint(h.n.z), (h.front ? 1u : 0u) | (sphere ? 0u : 2u), h.id >> 3, 0u};
+            }
+            uint4* const rec = (uint4*)io.hits + (size_t)j * 2u;
+            rec[0] = lo;
+            rec[1] = hi;
+        }
+        if (hit) {
+            uint32_t s = io.rng[j];
+            scatter<MODE>(P, s, ray, h);
+            io.rng[j] = s;
+            po[0] = ray.o.x; po[1] = ray.o.y; po[2] = ray.o.z;
+            pd[0] = ray.d.x; pd[1] = ray.d.y; pd[2] = ray.d.z;
+            if (io.throughput != nullptr) {
+                float* const pt = io.throughput + (size_t)j * 3u;
+                const f3 att = mk(pt[0], pt[1], pt[2]) * mk(h.ar * 0.7f, h.ag * 0.7f, h.ab * 0.7f);
+                pt[0] = att.x; pt[1] = att.y; pt[2] = att.z;
+            }
+        }
+    }
+    // (every lane of the wave that entered the kernel is here: none has returned)
+    if (io.count_out == nullptr) return;
+    const unsigned long long m = __ballot(hit);
+    if (hit) {  // (exec = the hitting lanes: the first active lane readfirstlane reads is the lowest bit of m, the leader)
+        uint32_t base = 0;
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll(m) - 1))
+            base = __hip_atomic_fetch_add(io.count_out, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (io.index_out != nullptr) io.index_out[base + rank] = j;  // rank: hitting lanes below this one
+    }
+}
+
 // The primary rays of one frame (rt_primary_rays): lane i is pixel (i % W, local row i / W) and stores the origin and
 // direction primary_ray<MODE> gives k_render for that pixel in the frame drawn at `time` (jitter, lens offset and, in the
 // triangle and mixed programs, the normalised direction included), packed 3 x f32. With `state` (rt_primary_rng) it stores
@@ -4506,6 +4576,41 @@ hipError_t hrt_launch_cast(int mode, int variant, const KParams& P, const float*
     default:
         if (P.tri_bvh) launch_cast_mode<MODE_MIXED, true>(variant, P, origins, dirs, n, h, grid, block, stream);
         else launch_cast_mode<MODE_MIXED, false>(variant, P, origins, dirs, n, h, grid, block, stream);
+        break;
+    }
+    return hipGetLastError();
+}
+
+// Host-side launcher of rt_bounce_rays: k_cast_rays' instantiation set and grid (one entry per lane; every step of a
+// loop is launched for the first step's n, the kernel reads *count_in).
+template <int MODE, bool TSAH>
+static void launch_bounce_mode(int variant, const KParams& P, const BounceIO& io, uint32_t n, dim3 grid, dim3 block,
+                               hipStream_t stream) {
+    if constexpr (MODE == MODE_TRIS) {
+        hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, io, n);
+    } else {
+        if (variant == SCAN_SIMPLE)
+            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, io, n);
+        else if (variant == SCAN_DEFER)
+            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, io, n);
+        else
+            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, io, n);
+    }
+}
+
+hipError_t hrt_launch_bounce(int mode, int variant, const KParams& P, const BounceIO& io, uint32_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    dim3 block(256);
+    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
+    switch (mode) {
+    case MODE_SPHERE: launch_bounce_mode<MODE_SPHERE, false>(variant, P, io, n, grid, block, stream); break;
+    case MODE_TRIS:
+        if (P.tri_bvh) launch_bounce_mode<MODE_TRIS, true>(variant, P, io, n, grid, block, stream);
+        else launch_bounce_mode<MODE_TRIS, false>(variant, P, io, n, grid, block, stream);
+        break;
+    default:
+        if (P.tri_bvh) launch_bounce_mode<MODE_MIXED, true>(variant, P, io, n, grid, block, stream);
+        else launch_bounce_mode<MODE_MIXED, false>(variant, P, io, n, grid, block, stream);
         break;
     }
     return hipGetLastError();

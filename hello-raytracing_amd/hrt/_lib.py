@@ -91,6 +91,25 @@ class RtStats(C.Structure):
     ]
 
 
+class RtBounce(C.Structure):
+    """include/hrt.h rt_bounce (88 B): the device buffers of one rt_bounce_rays step."""
+
+    _fields_ = [
+        ("origins_dev", C.c_void_p),
+        ("dirs_dev", C.c_void_p),
+        ("rng_dev", C.c_void_p),
+        ("throughput_dev", C.c_void_p),
+        ("queries_dev", C.c_void_p),
+        ("hits_dev", C.c_void_p),
+        ("index_in_dev", C.c_void_p),
+        ("count_in_dev", C.c_void_p),
+        ("index_out_dev", C.c_void_p),
+        ("count_out_dev", C.c_void_p),
+        ("paths", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 # Every exported symbol of include/hrt.h with its ctypes signature.
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -113,6 +132,7 @@ SIGNATURES = {
     "rt_occluded": (C.c_int, [_P, _P, _P, _P, _U32, _P]),
     "rt_primary_rays": (C.c_int, [_P, _U32, _P, _P, C.c_size_t]),
     "rt_trace_rays": (C.c_int, [_P, _P, _P, _P, _U32, _U32, _P, _P]),
+    "rt_bounce_rays": (C.c_int, [_P, C.POINTER(RtBounce), _U32]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),

@@ -555,6 +555,115 @@ class Renderer:
             return out[0].view(*o.shape), out[1].view(*o.shape[:2])
         return out.view(*o.shape)
 
+    def _bounce_buffer(self, t, name: str, shape, dtypes, optional: bool = False):
+        """A caller's state tensor of bounce_rays, checked: it is used in place, so nothing is converted or copied."""
+        import torch
+
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"bounce_rays: {name} is required")
+        dev = self._torch_device()
+        if not torch.is_tensor(t):
+            raise ValueError(f"bounce_rays: {name} must be a torch tensor on {dev} (it is used in place)")
+        if t.dtype not in dtypes or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError(f"bounce_rays: {name} must be {tuple(shape) if shape is not None else '(n,)'} "
+                             f"{dtypes[0]}, got {tuple(t.shape)} {t.dtype}")
+        if t.device != dev:
+            raise ValueError(f"bounce_rays: {name} is on {t.device}, the renderer draws on {dev}")
+        if not t.is_contiguous():
+            raise ValueError(f"bounce_rays: {name} must be contiguous (it is used in place)")
+        return t
+
+    def bounce_rays(self, origins, dirs, rng, throughput=None, queries=None, hits=None, index_in=None, count_in=None,
+                    index_out=None, count_out=None, n=None) -> None:
+        """rt_bounce_rays: one step of trace()'s loop, IN PLACE on the caller's torch tensors on the renderer's device.
+        origins, dirs: (paths, 3) float32; rng: (paths,) int32 (the 32 bits of the u32 state); throughput: (paths, 3)
+        float32; queries: (paths,) int32; hits: (paths, 8) int32 (the 32-byte rt_hit records, as cast_rays reads them);
+        index_in: (n,) int32 path indices (None: path i is entry i, n = paths); count_in / count_out: (1,) int32;
+        index_out: int32 with room for n entries. A path that hits gets its next ray, RNG state and throughput and is
+        appended to index_out; a path that misses is left untouched (include/hrt.h rt_bounce has the whole contract).
+        n (default: len(index_in), or paths) is the number of entries. Synchronises torch's current stream before the
+        call and the renderer after it."""
+        import torch
+
+        i32 = (torch.int32, getattr(torch, "uint32", torch.int32))
+        f32 = (torch.float32,)
+        o = self._bounce_buffer(origins, "origins", None, f32)
+        if o.ndim != 2 or o.shape[1] != 3:
+            raise ValueError(f"bounce_rays: origins must be (paths, 3) float32, got {tuple(o.shape)}")
+        paths = int(o.shape[0])
+        if paths >= 1 << 32:
+            raise ValueError("bounce_rays: at most 2^32 - 1 paths")
+        d = self._bounce_buffer(dirs, "dirs", (paths, 3), f32)
+        s = self._bounce_buffer(rng, "rng", (paths,), i32)
+        tp = self._bounce_buffer(throughput, "throughput", (paths, 3), f32, optional=True)
+        q = self._bounce_buffer(queries, "queries", (paths,), i32, optional=True)
+        h = self._bounce_buffer(hits, "hits", (paths, HIT_DTYPE.itemsize // 4), i32, optional=True)
+        ii = self._bounce_buffer(index_in, "index_in", None, i32, optional=True)
+        if ii is not None and ii.ndim != 1:
+            raise ValueError(f"bounce_rays: index_in must be (n,) int32, got {tuple(ii.shape)}")
+        if n is None:
+            n = int(ii.shape[0]) if ii is not None else paths
+        n = int(n)
+        if n < 0 or n >= 1 << 32 or (ii is not None and n > int(ii.shape[0])):
+            raise ValueError(f"bounce_rays: n = {n} entries for an index_in of "
+                             f"{int(ii.shape[0]) if ii is not None else paths}")
+        ci = self._bounce_buffer(count_in, "count_in", (1,), i32, optional=True)
+        io = self._bounce_buffer(index_out, "index_out", None, i32, optional=True)
+        if io is not None and (io.ndim != 1 or int(io.shape[0]) < n):
+            raise ValueError(f"bounce_rays: index_out must have room for {n} int32, got {tuple(io.shape)}")
+        co = self._bounce_buffer(count_out, "count_out", (1,), i32, optional=True)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        b = _lib.RtBounce(ptr(o), ptr(d), ptr(s), ptr(tp), ptr(q), ptr(h), ptr(ii), ptr(ci), ptr(io), ptr(co), paths, 0)
+        torch.cuda.current_stream(self._torch_device()).synchronize()
+        check(lib().rt_bounce_rays(self._h, C.byref(b), n), "bounce_rays")
+        self.synchronize()
+
+    def trace_wavefront(self, origins, dirs, rng, bounces: int, want_queries: bool = False):
+        """The wavefront form of trace_rays: `bounces` bounce_rays steps on copies of the given rays and states, the
+        survivors of each step handed to the next through two (index, count) pairs with no host read-back in between,
+        then 0.0 + throughput * sky with the sky of the GIVEN rays' d.y. Bit for bit trace_rays' radiance (and queries)
+        for rt_params.bounces = `bounces`. Returns (N, 3) float32 and, with want_queries, the (N,) int32 queries."""
+        import torch
+
+        o = self._rays_on_device(origins, "origins").clone()
+        d = self._rays_on_device(dirs, "dirs").clone()
+        if o.shape != d.shape:
+            raise ValueError(f"trace_wavefront: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
+        n = int(o.shape[0])
+        dev = self._torch_device()
+        s = rng
+        if not torch.is_tensor(s):
+            s = np.asarray(s)
+            if s.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+                raise ValueError(f"trace_wavefront: rng must be int32 or uint32, got {s.dtype}")
+            s = torch.from_numpy(np.ascontiguousarray(s).view(np.int32)).to(dev)
+        if s.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(s.shape) != (n,):
+            raise ValueError(f"trace_wavefront: rng must be ({n},) int32, got {tuple(s.shape)} {s.dtype}")
+        if s.device != dev:
+            raise ValueError(f"trace_wavefront: rng is on {s.device}, the renderer draws on {dev}")
+        s = s.contiguous().clone()
+        # the sky blend of trace()'s epilogue, one rounded f32 operation per operation of the kernels' expression
+        t = d[:, 1] * 0.5 + 0.5
+        u = 1.0 - t
+        sky = torch.stack((0.54 * u + 0.54 * t, 0.86 * u + 0.7 * t, 0.92 * u + 0.98 * t), dim=1)
+        att = torch.ones((n, 3), dtype=torch.float32, device=dev)
+        q = torch.zeros((n,), dtype=torch.int32, device=dev) if want_queries else None
+        index = [torch.empty((max(n, 1),), dtype=torch.int32, device=dev) for _ in range(2)]
+        count = [torch.zeros((1,), dtype=torch.int32, device=dev) for _ in range(2)]
+        if n > 0:
+            for k in range(int(bounces)):
+                src, dst = (k + 1) & 1, k & 1
+                self.bounce_rays(o, d, s, throughput=att, queries=q,
+                                 index_in=index[src] if k else None, count_in=count[src] if k else None,
+                                 index_out=index[dst], count_out=count[dst], n=n)
+        rad = 0.0 + att * sky
+        return (rad, q) if want_queries else rad
+
     def set_trace_rays_per_lane(self, rays_per_lane: int) -> None:
         """Test-only: k_radiance_rays' rays per lane, 0 = the host's rule (include/hrt_testing.h)."""
         check(lib().rt_testing_set_trace_rays_per_lane(self._h, rays_per_lane), "testing_set_trace_rays_per_lane")

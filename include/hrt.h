@@ -307,6 +307,52 @@ int rt_primary_rays(rt_renderer *r, uint32_t time, void *origins_dev, void *dirs
  * beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
 int rt_trace_rays(rt_renderer *r, const void *origins_dev, const void *dirs_dev, const void *rng_dev, uint32_t seed,
                   uint32_t n, void *radiance_dev, void *queries_dev);
+typedef struct rt_bounce {           /* every pointer: device memory on the renderer's GPU */
+    void *origins_dev, *dirs_dev;    /* paths x 3 f32, packed (4-byte aligned): read; overwritten for a path that hit */
+    void *rng_dev;                   /* paths u32: read; overwritten for a path that hit */
+    void *throughput_dev;            /* paths x 3 f32 or NULL: multiplied by albedo * 0.7 for a path that hit */
+    void *queries_dev;               /* paths u32 or NULL: += 1 for every path processed */
+    void *hits_dev;                  /* paths x 32 B rt_hit (16-byte aligned) or NULL: this step's hit record */
+    const void *index_in_dev;        /* n u32 path indices, or NULL = path i is entry i */
+    const void *count_in_dev;        /* one u32, or NULL: only the first min(n, *count_in) entries are processed */
+    void *index_out_dev;             /* room for n u32, or NULL: the indices of the paths that hit */
+    void *count_out_dev;             /* one u32, or NULL (required with index_out): how many paths hit */
+    uint32_t paths;                  /* entries in the state arrays; an index >= paths is skipped */
+    uint32_t reserved;               /* 0 */
+} rt_bounce;
+/* The path step: ONE iteration of trace()'s loop for paths whose state (ray, RNG state, throughput) the caller keeps in
+ * device memory between steps, with the paths that hit compacted into an index list for the next step — the wavefront
+ * counterpart of rt_trace_rays, for a caller's own integrator (shadow rays by rt_occluded between steps, per-bounce
+ * outputs, regrouping). Iterating it rt_params.bounces times from the rays of rt_primary_rays and the states of
+ * rt_primary_rng, with throughput started at 1, leaves throughput * sky equal to rt_trace_rays' radiance bit for bit and
+ * queries equal to its queries.
+ * Entry i of the n entries is path j = index_in ? index_in[i] : i. Only the first min(n, *count_in) entries are processed
+ * when count_in is given; an entry with j >= paths is skipped: nothing is read or written for it and it is not forwarded.
+ * For each processed path j:
+ *   - the query is the one rt_cast_rays documents, on (origins[j], dirs[j]): the sphere program's unnormalised d,
+ *     triangles from t >= 1e-4 and the |det| >= 1e-4 threshold, the reference walk's 600-step cap unless tri_bvh = 1, zero
+ *     padding slots counted as spheres, rt_params.variant / tri_bvh / min_sphere_slots; rt_params.bounces is not read (the
+ *     caller decides how many steps to take);
+ *   - on a hit, scatter advances rng[j] and replaces origins[j] and dirs[j], throughput[j] is multiplied component by
+ *     component by (albedo.r * 0.7, albedo.g * 0.7, albedo.b * 0.7) (throughput on the left, as trace() attenuates), and
+ *     j is appended to index_out and counted in *count_out;
+ *   - on a miss, origins[j], dirs[j], rng[j] and throughput[j] are left untouched, bit for bit, and j is not forwarded;
+ *   - either way queries[j] += 1, and hits[j] is the record rt_cast_rays would write for the ray BEFORE the scatter; both
+ *     only when the buffer is given.
+ * Compaction: *count_out is set to 0 on the renderer's stream before the kernel; index_out[0 .. *count_out - 1] receives
+ * exactly the forwarded indices, each once, and nothing past them is written. Order: entries of one 64-lane wave (entries
+ * 64 k .. 64 k + 63) keep their relative order; the order between waves is unspecified — compare as sets. count_out
+ * without index_out only counts.
+ * Aliasing: index_out must not overlap index_in and count_out must not be count_in: the caller ping-pongs between two
+ * (index, count) pairs (count_out == count_in is refused; an overlap of the index lists is not checked). Duplicate indices in index_in are the caller's error: the result is undefined and
+ * nothing checks for them.
+ * count_in exists so that a loop of steps needs no host read-back: launch every step with the first step's n and hand
+ * step k's count_out to step k + 1 as count_in.
+ * Asynchronous on the renderer's stream, as rt_cast_rays. n = 0 returns RT_OK and launches nothing. RT_ERR_ARG: n > 0 with
+ * a null io, origins, dirs or rng; index_out without count_out; index_in == NULL with n > paths; a misaligned buffer;
+ * reserved != 0; count_out == count_in. A scene state in which a draw fails gives the same status here; no camera is
+ * needed. Like the calls beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_bounce_rays(rt_renderer *r, const rt_bounce *io, uint32_t n);
 /* The RNG state fs_main holds after make_ray for each pixel of the frame drawn at `time` (the companion of
  * rt_primary_rays: same pixel order, same row partition): n_rays u32, 4-byte aligned device memory, asynchronous on the
  * renderer's stream. Needs a camera (RT_ERR_STATE otherwise); n_rays must equal local_rows x width (RT_ERR_ARG
@@ -387,8 +433,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
-                             rt_occluded, then rt_trace_rays / rt_primary_rng, came later without a new version (no struct
-                             changed): detect them by their symbols */
+                             rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, came later without a new
+                             version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

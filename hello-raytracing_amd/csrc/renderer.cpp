@@ -21,6 +21,7 @@
 #include "host/sphere_bvh.hpp"
 #include "host/tri_bvh.hpp"
 #include "rt_device.hpp"
+#include "rt_regroup.hpp"
 
 hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_accumulate(const hrt_dev::KParams& P, hipStream_t stream);
@@ -35,6 +36,7 @@ hipError_t hrt_launch_bounce(int mode, int variant, const hrt_dev::KParams& P, c
                              hipStream_t stream);
 hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
                                    uint32_t* state, hipStream_t stream);
+hipError_t hrt_launch_regroup(const hrt_regroup::Launch& a, uint32_t n, hipStream_t stream);  // rt_regroup.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -214,6 +216,8 @@ struct rt_renderer {
     uint32_t last_ordered = 0;  // trace launches of the last sample-queue draw that dealt in cost order
     DevBuf<unsigned long long> wave_trace;  // diagnostic build only
     size_t wave_trace_words = 0;
+    // rt_regroup_paths' sort: 4 u32 per entry, and the digit counts (rt_regroup.hpp Launch; include/hrt.h has the size rule)
+    DevBuf<uint32_t> regroup_entries, regroup_counts;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -243,7 +247,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes();
+               order_scratch.bytes() + regroup_entries.bytes() + regroup_counts.bytes();
     }
     uint32_t local_rows() const { return local_rows_of(height, params.row0, params.row_step, row_block()); }
     size_t image_floats() const { return (size_t)local_rows() * width * 3u; }
@@ -1449,6 +1453,65 @@ int rt_bounce_rays(rt_renderer* r, const rt_bounce* io, uint32_t n) {
     return RT_OK;
 }
 
+// Regrouping (include/hrt.h rt_regroup): the key pass and the radix sort of rt_regroup.hip in the renderer's own scratch.
+// No scene, camera or draw state is read.
+int rt_regroup_paths(rt_renderer* r, const rt_regroup* io, uint32_t n) {
+    if (!r) return fail(RT_ERR_ARG, "rt_regroup_paths: null");
+    if (n == 0) return RT_OK;
+    if (!io) return fail(RT_ERR_ARG, "rt_regroup_paths: null io");
+    if (io->mode != RT_REGROUP_CELL_OCTANT && io->mode != RT_REGROUP_KEYS)
+        return fail(RT_ERR_ARG, "rt_regroup_paths: unknown mode");
+    if (io->reserved != 0) return fail(RT_ERR_ARG, "rt_regroup_paths: reserved must be 0");
+    if (!io->index_out_dev) return fail(RT_ERR_ARG, "rt_regroup_paths: null index_out");
+    if (io->mode == RT_REGROUP_CELL_OCTANT && (!io->origins_dev || !io->dirs_dev))
+        return fail(RT_ERR_ARG, "rt_regroup_paths: mode 1 needs origins and dirs");
+    if (io->mode == RT_REGROUP_KEYS && !io->keys_dev) return fail(RT_ERR_ARG, "rt_regroup_paths: mode 2 needs keys");
+    if (n > RT_REGROUP_MAX_ENTRIES) return fail(RT_ERR_ARG, "rt_regroup_paths: more than RT_REGROUP_MAX_ENTRIES entries");
+    if (!io->index_in_dev && n > io->paths) return fail(RT_ERR_ARG, "rt_regroup_paths: n exceeds paths without index_in");
+    const bool cell = io->mode == RT_REGROUP_CELL_OCTANT;  // (a buffer the mode does not read is not looked at)
+    if ((cell && ((uintptr_t)io->origins_dev % 4u || (uintptr_t)io->dirs_dev % 4u)) || (!cell && (uintptr_t)io->keys_dev % 4u) ||
+        (uintptr_t)io->index_in_dev % 4u || (uintptr_t)io->count_in_dev % 4u || (uintptr_t)io->index_out_dev % 4u ||
+        (uintptr_t)io->keys_out_dev % 4u)
+        return fail(RT_ERR_ARG, "rt_regroup_paths: every buffer must be 4-byte aligned");
+    static_assert(sizeof(rt_regroup) == 96, "rt_regroup: seven pointers, two words, six floats, two words (hrt/_lib.py RtRegroup)");
+    hrt_regroup::Launch a{};
+    if (cell && !hrt_regroup::box_inverse(io->box_lo, io->box_hi, a.inv))
+        return fail(RT_ERR_ARG, "rt_regroup_paths: every box extent must be finite and at least 2^-60");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    const size_t tiles = ((size_t)n + RT_REGROUP_TILE - 1u) / RT_REGROUP_TILE;
+    int rc = ensure(r->regroup_entries, 4u * (size_t)n);
+    if (!rc) rc = ensure(r->regroup_counts, 256u * tiles + hrt_regroup::TAIL_WORDS);
+    if (rc) return rc;
+    a.origins = cell ? (const float*)io->origins_dev : nullptr;
+    a.dirs = cell ? (const float*)io->dirs_dev : nullptr;
+    a.keys = cell ? nullptr : (const uint32_t*)io->keys_dev;
+    a.index_in = (const uint32_t*)io->index_in_dev;
+    a.count_in = (const uint32_t*)io->count_in_dev;
+    a.index_out = (uint32_t*)io->index_out_dev;
+    a.keys_out = (uint32_t*)io->keys_out_dev;
+    a.paths = io->paths;
+    a.mode = io->mode;
+    for (int k = 0; k < 3; k++) a.lo[k] = cell ? io->box_lo[k] : 0.0f;
+    a.entries = r->regroup_entries.ptr;
+    a.counts = r->regroup_counts.ptr;
+    HIP_TRY(hrt_launch_regroup(a, n, r->stream));
+    return RT_OK;
+}
+
+int rt_host_regroup_keys(const float* origins, const float* dirs, uint32_t n, const float box_lo[3], const float box_hi[3],
+                         uint32_t* keys_out) {
+    if (!box_lo || !box_hi) return fail(RT_ERR_ARG, "rt_host_regroup_keys: null box");
+    float inv[3];
+    if (!hrt_regroup::box_inverse(box_lo, box_hi, inv))
+        return fail(RT_ERR_ARG, "rt_host_regroup_keys: every box extent must be finite and at least 2^-60");
+    if (n == 0) return RT_OK;
+    if (!origins || !dirs || !keys_out) return fail(RT_ERR_ARG, "rt_host_regroup_keys: null buffer");
+    for (uint32_t i = 0; i < n; i++)
+        keys_out[i] = hrt_regroup::cell_octant_key(origins + 3u * (size_t)i, dirs + 3u * (size_t)i, box_lo, inv);
+    return RT_OK;
+}
+
 int rt_primary_rays(rt_renderer* r, uint32_t time, void* origins_dev, void* dirs_dev, size_t n_rays) {
     if (!r) return fail(RT_ERR_ARG, "rt_primary_rays: null");
     if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before rt_primary_rays");
@@ -1560,6 +1623,8 @@ int rt_release_scratch(rt_renderer* r) {
     r->samples2.release();
     r->ring.release();
     r->ring_ctl.release();
+    r->regroup_entries.release();
+    r->regroup_counts.release();
     return RT_OK;
 }
 

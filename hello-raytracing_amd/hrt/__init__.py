@@ -4,7 +4,7 @@ The compute path is lib/libhrt.so (HIP kernels for gfx950 behind the C-ABI of in
 package is the host-side mirror of the reference's Rust scene API plus ctypes plumbing.
 """
 from . import _lib
-from ._lib import (RT_HIT_FRONT, RT_HIT_TRIANGLE, RT_T_MISS, UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
+from ._lib import (REGROUP_CELL_OCTANT, REGROUP_KEYS, REGROUP_TILE, RtRegroup, RT_HIT_FRONT, RT_HIT_TRIANGLE, RT_T_MISS, UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
                    lib)
 from .scene import (CAMERA_DTYPE, HIT_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
@@ -27,6 +27,28 @@ def check_uniform_guards(n_waves: int, seed: int) -> dict:
     _lib.check(lib().rt_check_uniform_guards(int(n_waves), int(seed) & 0xFFFFFFFF, out), "rt_check_uniform_guards")
     w = len(UGUARD_COLUMNS)
     return {h: {c: int(out[i * w + j]) for j, c in enumerate(UGUARD_COLUMNS)} for i, h in enumerate(UGUARD_HELPERS)}
+
+
+def regroup_keys(origins, dirs, lo, hi):
+    """rt_host_regroup_keys (include/hrt.h): rt_regroup_paths' 24-bit cell-and-octant key of each of n rays, on the host
+    (no device): (n, 3) float32 origins and directions and the box (lo, hi) the origins are quantised in -> (n,) uint32.
+    Raises RtError for a bad box (an extent that is not finite or below 2^-60)."""
+    import ctypes as C
+
+    import numpy as np
+
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f"regroup_keys: {o.shape} origins for {d.shape} directions")
+    blo = np.ascontiguousarray(lo, dtype=np.float32).reshape(3)
+    bhi = np.ascontiguousarray(hi, dtype=np.float32).reshape(3)
+    out = np.empty((o.shape[0],), dtype=np.uint32)
+    pf = C.POINTER(C.c_float)
+    _lib.check(lib().rt_host_regroup_keys(o.ctypes.data_as(pf), d.ctypes.data_as(pf), o.shape[0], blo.ctypes.data_as(pf),
+                                          bhi.ctypes.data_as(pf), out.ctypes.data_as(C.POINTER(C.c_uint32))),
+               "rt_host_regroup_keys")
+    return out
 
 
 def sphere_bvh_leaves(spheres, min_sphere_slots: int = 0) -> dict:
@@ -59,5 +81,5 @@ __all__ = [
     "PI", "SPHERE_DTYPE", "TRIANGLE_DTYPE", "Camera", "ComparisonError", "Material", "Mesh", "OrbitCamera", "Renderer",
     "SceneSphere", "SceneTris", "Sphere", "Tree", "Vec3", "compare_ppm_images", "f32", "ppm_from_image",
     "read_asset", "render_ppm", "spheres_array", "device_count", "check_uniform_guards", "UGUARD_COLUMNS", "UGUARD_HELPERS",
-    "sphere_bvh_leaves",
+    "sphere_bvh_leaves", "regroup_keys", "REGROUP_CELL_OCTANT", "REGROUP_KEYS", "REGROUP_TILE", "RtRegroup",
 ]

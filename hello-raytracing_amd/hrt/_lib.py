@@ -110,6 +110,33 @@ class RtBounce(C.Structure):
     ]
 
 
+# rt_regroup_paths (include/hrt.h): the modes, and the entries per workgroup of the sort's count and scatter kernels
+REGROUP_CELL_OCTANT = 1
+REGROUP_KEYS = 2
+REGROUP_MAX_ENTRIES = 1 << 28
+REGROUP_TILE = 1024
+
+
+class RtRegroup(C.Structure):
+    """include/hrt.h rt_regroup (96 B): the device buffers and the key mode of one rt_regroup_paths call."""
+
+    _fields_ = [
+        ("origins_dev", C.c_void_p),
+        ("dirs_dev", C.c_void_p),
+        ("keys_dev", C.c_void_p),
+        ("index_in_dev", C.c_void_p),
+        ("count_in_dev", C.c_void_p),
+        ("index_out_dev", C.c_void_p),
+        ("keys_out_dev", C.c_void_p),
+        ("paths", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("box_lo", C.c_float * 3),
+        ("box_hi", C.c_float * 3),
+        ("reserved", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
 # Every exported symbol of include/hrt.h with its ctypes signature.
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -133,6 +160,8 @@ SIGNATURES = {
     "rt_primary_rays": (C.c_int, [_P, _U32, _P, _P, C.c_size_t]),
     "rt_trace_rays": (C.c_int, [_P, _P, _P, _P, _U32, _U32, _P, _P]),
     "rt_bounce_rays": (C.c_int, [_P, C.POINTER(RtBounce), _U32]),
+    "rt_regroup_paths": (C.c_int, [_P, C.POINTER(RtRegroup), _U32]),
+    "rt_host_regroup_keys": (C.c_int, [_PF, _PF, _U32, _PF, _PF, _PU32]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),

@@ -555,24 +555,25 @@ class Renderer:
             return out[0].view(*o.shape), out[1].view(*o.shape[:2])
         return out.view(*o.shape)
 
-    def _bounce_buffer(self, t, name: str, shape, dtypes, optional: bool = False):
-        """A caller's state tensor of bounce_rays, checked: it is used in place, so nothing is converted or copied."""
+    def _bounce_buffer(self, t, name: str, shape, dtypes, optional: bool = False, who: str = "bounce_rays"):
+        """A caller's state tensor of bounce_rays (or of `who`, for the messages), checked: it is used in place, so nothing
+        is converted or copied."""
         import torch
 
         if t is None:
             if optional:
                 return None
-            raise ValueError(f"bounce_rays: {name} is required")
+            raise ValueError(f"{who}: {name} is required")
         dev = self._torch_device()
         if not torch.is_tensor(t):
-            raise ValueError(f"bounce_rays: {name} must be a torch tensor on {dev} (it is used in place)")
+            raise ValueError(f"{who}: {name} must be a torch tensor on {dev} (it is used in place)")
         if t.dtype not in dtypes or (shape is not None and tuple(t.shape) != tuple(shape)):
-            raise ValueError(f"bounce_rays: {name} must be {tuple(shape) if shape is not None else '(n,)'} "
+            raise ValueError(f"{who}: {name} must be {tuple(shape) if shape is not None else '(n,)'} "
                              f"{dtypes[0]}, got {tuple(t.shape)} {t.dtype}")
         if t.device != dev:
-            raise ValueError(f"bounce_rays: {name} is on {t.device}, the renderer draws on {dev}")
+            raise ValueError(f"{who}: {name} is on {t.device}, the renderer draws on {dev}")
         if not t.is_contiguous():
-            raise ValueError(f"bounce_rays: {name} must be contiguous (it is used in place)")
+            raise ValueError(f"{who}: {name} must be contiguous (it is used in place)")
         return t
 
     def bounce_rays(self, origins, dirs, rng, throughput=None, queries=None, hits=None, index_in=None, count_in=None,
@@ -623,11 +624,80 @@ class Renderer:
         check(lib().rt_bounce_rays(self._h, C.byref(b), n), "bounce_rays")
         self.synchronize()
 
-    def trace_wavefront(self, origins, dirs, rng, bounces: int, want_queries: bool = False):
+    def regroup_paths(self, index_out, origins=None, dirs=None, keys=None, box=None, index_in=None, count_in=None,
+                      keys_out=None, n=None, paths=None) -> None:
+        """rt_regroup_paths: sort a path index list by a coherence key, IN PLACE on the caller's torch tensors on the
+        renderer's device (include/hrt.h rt_regroup has the whole contract). Exactly one of
+          box=(lo, hi): the 24-bit cell-and-octant key of each path's ray, from origins and dirs ((paths, 3) float32) and
+                        the box the origins are quantised in (hrt.regroup_keys gives the same keys on the host);
+          keys:         (paths,) int32, the caller's own 32-bit keys, indexed by path.
+        index_in: (n,) int32 path indices (None: entry i is path i); count_in: (1,) int32, only the first
+        min(n, count_in) entries are sorted; index_out: int32 with room for n entries — index_in itself for a sort in
+        place; keys_out: int32 with room for n, the key of each output entry. The sort is stable. n (default:
+        len(index_in), or paths) is the number of entries; paths (default: the rows of origins or keys) the number of
+        paths behind the indices. Synchronises torch's current stream before the call and the renderer after it."""
+        import torch
+
+        who = "regroup_paths"
+        i32 = (torch.int32, getattr(torch, "uint32", torch.int32))
+        f32 = (torch.float32,)
+        if (box is None) == (keys is None):
+            raise ValueError("regroup_paths: give exactly one of box=(lo, hi) (with origins and dirs) and keys")
+        o = d = kk = None
+        lo = hi = (0.0, 0.0, 0.0)
+        if box is not None:
+            lo, hi = (tuple(float(x) for x in b) for b in box)
+            if len(lo) != 3 or len(hi) != 3:
+                raise ValueError("regroup_paths: box must be ((x, y, z), (x, y, z))")
+            o = self._bounce_buffer(origins, "origins", None, f32, who=who)
+            if o.ndim != 2 or o.shape[1] != 3:
+                raise ValueError(f"regroup_paths: origins must be (paths, 3) float32, got {tuple(o.shape)}")
+            d = self._bounce_buffer(dirs, "dirs", tuple(o.shape), f32, who=who)
+            rows = int(o.shape[0])
+        else:
+            kk = self._bounce_buffer(keys, "keys", None, i32, who=who)
+            if kk.ndim != 1:
+                raise ValueError(f"regroup_paths: keys must be (paths,) int32, got {tuple(kk.shape)}")
+            rows = int(kk.shape[0])
+        paths = rows if paths is None else int(paths)
+        if paths < 0 or paths > rows:
+            raise ValueError(f"regroup_paths: paths = {paths} for state arrays of {rows} rows")
+        ii = self._bounce_buffer(index_in, "index_in", None, i32, optional=True, who=who)
+        if ii is not None and ii.ndim != 1:
+            raise ValueError(f"regroup_paths: index_in must be (n,) int32, got {tuple(ii.shape)}")
+        if n is None:
+            n = int(ii.shape[0]) if ii is not None else paths
+        n = int(n)
+        if n < 0 or n >= 1 << 32 or (ii is not None and n > int(ii.shape[0])):
+            raise ValueError(f"regroup_paths: n = {n} entries for an index_in of "
+                             f"{int(ii.shape[0]) if ii is not None else paths}")
+        ci = self._bounce_buffer(count_in, "count_in", (1,), i32, optional=True, who=who)
+        io = self._bounce_buffer(index_out, "index_out", None, i32, who=who)
+        if io.ndim != 1 or int(io.shape[0]) < n:
+            raise ValueError(f"regroup_paths: index_out must have room for {n} int32, got {tuple(io.shape)}")
+        ko = self._bounce_buffer(keys_out, "keys_out", None, i32, optional=True, who=who)
+        if ko is not None and (ko.ndim != 1 or int(ko.shape[0]) < n):
+            raise ValueError(f"regroup_paths: keys_out must have room for {n} int32, got {tuple(ko.shape)}")
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        g = _lib.RtRegroup(ptr(o), ptr(d), ptr(kk), ptr(ii), ptr(ci), ptr(io), ptr(ko), paths,
+                           _lib.REGROUP_CELL_OCTANT if box is not None else _lib.REGROUP_KEYS,
+                           (C.c_float * 3)(*lo), (C.c_float * 3)(*hi), 0, 0)
+        torch.cuda.current_stream(self._torch_device()).synchronize()
+        check(lib().rt_regroup_paths(self._h, C.byref(g), n), "regroup_paths")
+        self.synchronize()
+
+    def trace_wavefront(self, origins, dirs, rng, bounces: int, want_queries: bool = False, regroup_box=None,
+                        regroup_after=()):
         """The wavefront form of trace_rays: `bounces` bounce_rays steps on copies of the given rays and states, the
         survivors of each step handed to the next through two (index, count) pairs with no host read-back in between,
         then 0.0 + throughput * sky with the sky of the GIVEN rays' d.y. Bit for bit trace_rays' radiance (and queries)
-        for rt_params.bounces = `bounces`. Returns (N, 3) float32 and, with want_queries, the (N,) int32 queries."""
+        for rt_params.bounces = `bounces`. Returns (N, 3) float32 and, with want_queries, the (N,) int32 queries.
+        regroup_box=(lo, hi) with regroup_after, the 1-based steps after which the survivors' list is regrouped in place
+        (regroup_paths by the cell-and-octant key, index_out = index_in, the step's own count buffer): the order of the
+        list changes, the result does not."""
         import torch
 
         o = self._rays_on_device(origins, "origins").clone()
@@ -655,12 +725,18 @@ class Renderer:
         q = torch.zeros((n,), dtype=torch.int32, device=dev) if want_queries else None
         index = [torch.empty((max(n, 1),), dtype=torch.int32, device=dev) for _ in range(2)]
         count = [torch.zeros((1,), dtype=torch.int32, device=dev) for _ in range(2)]
+        regroup_after = frozenset(int(k) for k in regroup_after)
+        if regroup_after and regroup_box is None:
+            raise ValueError("trace_wavefront: regroup_after needs regroup_box=(lo, hi)")
         if n > 0:
             for k in range(int(bounces)):
                 src, dst = (k + 1) & 1, k & 1
                 self.bounce_rays(o, d, s, throughput=att, queries=q,
                                  index_in=index[src] if k else None, count_in=count[src] if k else None,
                                  index_out=index[dst], count_out=count[dst], n=n)
+                if k + 1 in regroup_after:
+                    self.regroup_paths(index[dst], origins=o, dirs=d, box=regroup_box, index_in=index[dst],
+                                       count_in=count[dst], n=n)
         rad = 0.0 + att * sky
         return (rad, q) if want_queries else rad
 

@@ -353,6 +353,61 @@ typedef struct rt_bounce {           /* every pointer: device memory on the rend
  * reserved != 0; count_out == count_in. A scene state in which a draw fails gives the same status here; no camera is
  * needed. Like the calls beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
 int rt_bounce_rays(rt_renderer *r, const rt_bounce *io, uint32_t n);
+#define RT_REGROUP_CELL_OCTANT 1u   /* 24-bit key from the path's ray and a caller's box (below) */
+#define RT_REGROUP_KEYS        2u   /* 32-bit keys the caller supplies per path                  */
+#define RT_REGROUP_MAX_ENTRIES (1u << 28)
+#define RT_REGROUP_TILE        1024u /* entries per workgroup of the sort's count and scatter kernels */
+typedef struct rt_regroup {          /* every pointer: device memory on the renderer's GPU */
+    const void *origins_dev, *dirs_dev; /* paths x 3 f32, packed: read (mode 1); unused and may be NULL in mode 2 */
+    const void *keys_dev;            /* paths u32, indexed by PATH: read (mode 2); unused and may be NULL in mode 1 */
+    const void *index_in_dev;        /* n u32 path indices, or NULL = entry i is path i */
+    const void *count_in_dev;        /* one u32 or NULL: only the first min(n, *count_in) entries are sorted */
+    void *index_out_dev;             /* room for n u32: the same indices, in key order */
+    void *keys_out_dev;              /* room for n u32 or NULL: the key of each output entry */
+    uint32_t paths, mode;
+    float box_lo[3], box_hi[3];      /* mode 1: the box the origins are quantised in */
+    uint32_t reserved;               /* 0 */
+    uint32_t pad;                    /* not read: makes sizeof 96, a multiple of the pointers' 8 bytes */
+} rt_regroup;
+/* Regrouping: sorts a path index list by a coherence key, on the device, so that the lanes of a wave of the next
+ * rt_bounce_rays step walk neighbouring parts of the scene (or share whatever the caller's keys say they share). The live
+ * count stays on the device and the result goes straight into the next step as index_in: no read-back, like count_in.
+ * Entries: live = min(n, *count_in), or n without count_in. Entry i < live is path j = index_in ? index_in[i] : i.
+ * Output: index_out[0 .. live - 1] is a permutation of those j in ascending key order; entries with equal keys keep their
+ * input order (the sort is stable), so given its inputs the result is fully determined, bit for bit. keys_out[k], when
+ * given, is the key of index_out[k]. Nothing is written at or past position live of either output, and no other buffer of
+ * the caller's is written. There is no count_out: the count does not change, and the caller hands the same count buffer
+ * to the next step.
+ * Keys: an entry with j >= paths is kept, with the largest key of the mode (0x00FFFFFF in mode 1, 0xFFFFFFFF in mode 2), so
+ * it sorts into the last group; nothing is read through such an index (rt_bounce_rays skips it later anyway). Duplicate
+ * indices are not an error here: each entry is sorted on its own.
+ *   RT_REGROUP_CELL_OCTANT (mode 1): 24 bits from (origins[j], dirs[j]) and the box, computed in f32 with no FMA, the same
+ *     inline function on host and device. The host computes inv_k = 128.0f / (box_hi[k] - box_lo[k]) per axis (the IEEE
+ *     division); per axis f = (o_k - box_lo[k]) * inv_k, two rounded operations, and
+ *     q_k = !(f > 0) ? 0 : (f >= 128 ? 127 : (uint32_t)f), so NaN and -inf give 0 and +inf gives 127. Bit i of q_x, q_y, q_z
+ *     goes to key bit 3 + 3i, 4 + 3i, 5 + 3i (a Morton code of the cell in a 128^3 grid over the box); key bits 0, 1, 2
+ *     are the raw sign bits of d.x, d.y, d.z, read from the bit pattern (-0 and a negative NaN count as negative). The rays
+ *     of one cell that point into the same octant end up next to each other. A bad box is RT_ERR_ARG: every
+ *     box_hi[k] - box_lo[k] must be finite and >= 2^-60, and every inv_k finite. rt_host_regroup_keys gives the same keys
+ *     on the host.
+ *   RT_REGROUP_KEYS (mode 2): keys[j], all 32 bits (the material or primitive of rt_bounce's hits, a caller's own cell).
+ * Aliasing: index_out == index_in, the same pointer, is allowed: regrouping in place between two steps (every read of
+ * index_in happens before the first write of index_out). Any other overlap of the two is undefined. keys_out must not
+ * overlap any input.
+ * Scratch: the sort (a stable least-significant-digit radix sort over 8-bit digits, 3 passes in mode 1 and 4 in mode 2)
+ * works in memory the renderer owns, grown on demand and kept for the next call: 4 u32 per entry of the largest n so far,
+ * plus 256 u32 of digit counts per RT_REGROUP_TILE entries of it (rounded up), plus 1040 u32. rt_release_scratch and
+ * rt_destroy free it.
+ * Asynchronous on the renderer's stream, as rt_cast_rays; every kernel is launched for the caller's n and reads the count
+ * on the device. n = 0 returns RT_OK and launches nothing. RT_ERR_ARG: a null io or index_out; a null origins or dirs in
+ * mode 1; a null keys in mode 2; an unknown mode; reserved != 0; a misaligned buffer (4 bytes); index_in == NULL with
+ * n > paths; n > RT_REGROUP_MAX_ENTRIES; a bad box in mode 1. It needs no scene and no camera and works in any scene
+ * state. Like the calls beside it, it touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_regroup_paths(rt_renderer *r, const rt_regroup *io, uint32_t n);
+/* The key of mode 1 on the host, for n rays: pure CPU, no device. origins / dirs: n x 3 f32, packed; keys_out: n u32.
+ * RT_ERR_ARG for a null pointer with n > 0 or a bad box (as rt_regroup_paths). */
+int rt_host_regroup_keys(const float *origins, const float *dirs, uint32_t n, const float box_lo[3],
+                         const float box_hi[3], uint32_t *keys_out);
 /* The RNG state fs_main holds after make_ray for each pixel of the frame drawn at `time` (the companion of
  * rt_primary_rays: same pixel order, same row partition): n_rays u32, 4-byte aligned device memory, asynchronous on the
  * renderer's stream. Needs a camera (RT_ERR_STATE otherwise); n_rays must equal local_rows x width (RT_ERR_ARG
@@ -433,8 +488,9 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
  * the two sizes against its own sizeof) before the first rt_set_params / rt_get_stats. Any pointer may be NULL. */
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
-                             rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, came later without a new
-                             version (no struct changed): detect them by their symbols */
+                             rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, then rt_regroup_paths /
+                             rt_host_regroup_keys, came later without a new version (no struct changed): detect them by
+                             their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

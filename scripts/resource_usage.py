@@ -1,4 +1,4 @@
-"""Compiler resource usage of every product kernel (VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy), from
+"""Compiler resource usage of every product kernel of both device translation units (rt_kernels.hip, rt_regroup.hip) (VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy), from
 hipcc -Rpass-analysis=kernel-resource-usage with the product flags (hello-raytracing_amd/Makefile).
 
 usage: python scripts/resource_usage.py [extra hipcc flags ...] > profiles/rNN/resource_usage.txt
@@ -17,10 +17,14 @@ KEYS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("VGPRs Sp
 
 
 def main() -> int:
-    src = ROOT / "hello-raytracing_amd" / "csrc" / "rt_kernels.hip"
-    cmd = ["/opt/rocm/bin/hipcc", *FLAGS, *sys.argv[1:], str(src), "-o", "/tmp/hrt_ru.o",
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    # one translation unit after the other: rt_kernels.hip's rows first, as before; then rt_regroup.hip's
+    csrc = ROOT / "hello-raytracing_amd" / "csrc"
+    out, cmds = "", []
+    for src in (csrc / "rt_kernels.hip", csrc / "rt_regroup.hip"):
+        cmd = ["/opt/rocm/bin/hipcc", *FLAGS, *sys.argv[1:], str(src), "-o", "/tmp/hrt_ru.o",
+               "-Rpass-analysis=kernel-resource-usage"]
+        out += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+        cmds.append(cmd)
     rows, cur = [], None
     for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
@@ -35,7 +39,8 @@ def main() -> int:
             if m and cur is not None and short not in cur:
                 cur[short] = int(m.group(1))
     cols = ["kernel"] + [s for _, s in KEYS]
-    print("# " + " ".join(cmd[:-1]))
+    for cmd in cmds:
+        print("# " + " ".join(cmd[:-1]))
     print("\t".join(cols))
     for r in rows:
         print("\t".join(str(r.get(c, "")) for c in cols))

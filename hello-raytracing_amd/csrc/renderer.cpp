@@ -21,6 +21,7 @@
 #include "host/sphere_bvh.hpp"
 #include "host/tri_bvh.hpp"
 #include "rt_device.hpp"
+#include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
 
 hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
@@ -37,6 +38,7 @@ hipError_t hrt_launch_bounce(int mode, int variant, const hrt_dev::KParams& P, c
 hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t time, float* origins, float* dirs,
                                    uint32_t* state, hipStream_t stream);
 hipError_t hrt_launch_regroup(const hrt_regroup::Launch& a, uint32_t n, hipStream_t stream);  // rt_regroup.hip
+hipError_t hrt_launch_lbvh(const hrt_lbvh::Launch& a, hipStream_t stream);                     // rt_lbvh.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -195,6 +197,20 @@ struct rt_renderer {
     hrt::TriBvh tri_tree;
     DevBuf<uint4> tb_hnodes;
     DevBuf<uint32_t> tb_order;
+    uint32_t tb_n_nodes = 0, tb_n_order = 0;  // nodes (2 uint4 each) and leaf positions the two buffers hold
+    // rt_set_triangles_device: true = device geometry (tris, tri_geo and the tree were made on the device: there is no
+    // reference heap and no tri_aee, and every draw and query walks the tree whatever rt_params.tri_bvh says; tri_tree
+    // holds only the root word, centre, radius and depth). rt_set_bvh leaves the state.
+    bool dev_geom = false;
+    // its staging buffers (a build writes these; success swaps them with tris, tri_geo, mats, tb_hnodes and tb_order, so
+    // they then hold the geometry before: two sets that alternate for a mesh that moves every step) and its scratch
+    // (rt_lbvh.hpp Launch): keys and sorted keys, parent links, arrival counters, box slots, the status block
+    DevBuf<hrt_dev::TriDev> lb_tris;
+    DevBuf<float> lb_geo;
+    DevBuf<hrt_dev::MatDev> lb_mats;
+    DevBuf<uint4> lb_hnodes;
+    DevBuf<uint32_t> lb_order, lb_keys, lb_parent, lb_arrivals;
+    DevBuf<uint64_t> lb_boxes, lb_stat;
     DevBuf<unsigned long long> counter;
     DevBuf<unsigned long long> count_spread;  // the work counters' CSPREAD copies (rt_kernels.hip flush_counts)
     DevBuf<unsigned long long> steal_slots;  // sample queue: one word per resident wave (frame-block work stealing)
@@ -247,7 +263,9 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + regroup_entries.bytes() + regroup_counts.bytes();
+               order_scratch.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
+               lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
     uint32_t local_rows() const { return local_rows_of(height, params.row0, params.row_step, row_block()); }
     size_t image_floats() const { return (size_t)local_rows() * width * 3u; }
@@ -267,6 +285,18 @@ hrt_dev::DielConsts dielectric_consts(float param) {
     };
     const float inv = 1.0f / param;
     return hrt_dev::DielConsts{inv, r0sq(inv), r0sq(param)};
+}
+
+// rt_set_bvh's and rt_set_triangles_device's materials as the kernels read them.
+std::vector<hrt_dev::MatDev> pack_materials(const void* mats32, uint32_t n_mats) {
+    const hrt::Material* M = (const hrt::Material*)mats32;
+    std::vector<hrt_dev::MatDev> md(n_mats);
+    for (uint32_t k = 0; k < n_mats; k++) {
+        const hrt_dev::DielConsts dc = dielectric_consts(M[k].params.x);
+        md[k] = hrt_dev::MatDev{M[k].albedo.x, M[k].albedo.y, M[k].albedo.z, M[k].params.x, M[k].kind,
+                                dc.inv_param, dc.r0sq_front, dc.r0sq_back};
+    }
+    return md;
 }
 
 int zero_image(rt_renderer* r) {
@@ -317,20 +347,8 @@ std::vector<float> pack_nodes_so(const float* nodes, uint32_t n, bool& so_ok) {
 // box relative to `center` as six halves rounded outward (min down, max up: containment holds, so the walk
 // stays exact; the boxes only grow by at most one half ulp), then the child word:
 //   (min.x | min.y << 16, min.z | max.x << 16, max.y | max.z << 16, left word), the same for the right.
-uint16_t f16_bits(_Float16 h) { return __builtin_bit_cast(uint16_t, h); }
-_Float16 f16_from_bits(uint16_t b) { return __builtin_bit_cast(_Float16, b); }
-_Float16 f16_step(_Float16 h, bool up) {
-    uint16_t b = f16_bits(h);
-    if ((b & 0x7FFFu) == 0u) return f16_from_bits(up ? 0x0001u : 0x8001u);  // +-0 -> smallest subnormal
-    const bool neg = (b & 0x8000u) != 0u;
-    b = (uint16_t)((up != neg) ? b + 1u : b - 1u);
-    return f16_from_bits(b);
-}
-uint32_t f16_dir(float x, bool up) {
-    _Float16 h = (_Float16)x;
-    if (up ? (float)h < x : (float)h > x) h = f16_step(h, up);
-    return f16_bits(h);
-}
+// (f16_dir: rt_lbvh.hpp, shared with the device-built triangle tree)
+using hrt_lbvh::f16_dir;
 std::vector<uint4> pack_bvh_hnodes(const std::vector<hrt::SphereBvhNode>& nodes, const float center[3]) {
     std::vector<uint4> out(2 * std::max<size_t>(nodes.size(), 1), uint4{0u, 0u, 0u, 0u});
     auto rel = [&](float v, int k, bool up) {
@@ -353,7 +371,7 @@ std::vector<uint4> pack_bvh_hnodes(const std::vector<hrt::SphereBvhNode>& nodes,
 }
 
 int upload_tri_tree(rt_renderer* r) {
-    if (!r->tri_tree_dirty) return RT_OK;
+    if (r->dev_geom || !r->tri_tree_dirty) return RT_OK;  // (device geometry: the tree is there, and tri_aee is not)
     r->tri_tree = hrt::build_tri_bvh(r->tri_aee);
     const std::vector<uint4> hpacked = pack_bvh_hnodes(r->tri_tree.nodes, r->tri_tree.root_center);
     int rc = ensure(r->tb_hnodes, hpacked.size());
@@ -365,8 +383,16 @@ int upload_tri_tree(rt_renderer* r) {
         HIP_TRY(hipMemcpyAsync(r->tb_order.ptr, r->tri_tree.order.data(), r->tri_tree.order.size() * sizeof(uint32_t),
                                hipMemcpyHostToDevice, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
+    r->tb_n_nodes = (uint32_t)r->tri_tree.nodes.size();
+    r->tb_n_order = (uint32_t)r->tri_tree.order.size();
     r->tri_tree_dirty = false;
     return RT_OK;
+}
+
+template <typename T>
+void swap_buffers(DevBuf<T>& a, DevBuf<T>& b) {
+    std::swap(a.ptr, b.ptr);
+    std::swap(a.cap, b.cap);
 }
 
 int upload_spheres(rt_renderer* r) {
@@ -543,7 +569,7 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     P.so_ok = r->so_ok ? 1u : 0u;
     P.tris = r->tris.ptr;
     P.tri_geo = r->tri_geo.ptr;
-    P.tri_bvh = (r->mode != RT_MODE_SPHERE && r->params.tri_bvh) ? 1u : 0u;
+    P.tri_bvh = (r->mode != RT_MODE_SPHERE && (r->params.tri_bvh || r->dev_geom)) ? 1u : 0u;
     if (P.tri_bvh) {
         int rc = upload_tri_tree(r);
         if (rc) return rc;
@@ -1024,6 +1050,16 @@ void delete_buffers(rt_renderer* r) {
     r->mats.release();
     r->tb_hnodes.release();
     r->tb_order.release();
+    r->lb_tris.release();
+    r->lb_geo.release();
+    r->lb_mats.release();
+    r->lb_hnodes.release();
+    r->lb_order.release();
+    r->lb_keys.release();
+    r->lb_parent.release();
+    r->lb_arrivals.release();
+    r->lb_boxes.release();
+    r->lb_stat.release();
     r->counter.release();
     r->count_spread.release();
     r->steal_slots.release();
@@ -1229,14 +1265,7 @@ int rt_set_bvh(rt_renderer* r, const uint32_t sizes[2], const void* nodes32, uin
         std::copy(v, v + 9, &r->tri_aee[9 * (size_t)j]);
     }
     r->tri_tree_dirty = true;
-    const hrt::Material* M = (const hrt::Material*)mats32;
-    std::vector<hrt_dev::MatDev> md(n_mats);
-    for (uint32_t k = 0; k < n_mats; k++)
-    {
-        const hrt_dev::DielConsts dc = dielectric_consts(M[k].params.x);
-        md[k] = hrt_dev::MatDev{M[k].albedo.x, M[k].albedo.y, M[k].albedo.z, M[k].params.x, M[k].kind,
-                                dc.inv_param, dc.r0sq_front, dc.r0sq_back};
-    }
+    const std::vector<hrt_dev::MatDev> md = pack_materials(mats32, n_mats);
     // The sign-ordered copy (36 B per node) only where a kernel reads it: the heap-top kernels run for heaps of at
     // most 2^24 nodes (launch_frames, tri_small); a larger tree would pay up to ~2.4 GB of host and device memory
     // for nothing
@@ -1264,6 +1293,144 @@ int rt_set_bvh(rt_renderer* r, const uint32_t sizes[2], const void* nodes32, uin
     r->bvh_n = n;
     r->bvh_m = m;
     r->so_ok = so_ok;
+    r->dev_geom = false;  // (the heap and tri_aee are back: tri_bvh chooses the walk again)
+    return RT_OK;
+}
+
+// Triangles from device memory, with an LBVH built for them on the device (include/hrt.h; rt_lbvh.hip, rt_lbvh.hpp).
+// Everything is written to the staging buffers and swapped in after the status block says the build is good.
+int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_tris, const void* mats32, uint32_t n_mats) {
+    if (!r) return fail(RT_ERR_ARG, "rt_set_triangles_device: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_set_triangles_device: the sphere program has no triangles");
+    if (n_tris && !tris64_dev) return fail(RT_ERR_ARG, "rt_set_triangles_device: null triangles");
+    if ((uintptr_t)tris64_dev % 16u) return fail(RT_ERR_ARG, "rt_set_triangles_device: triangles must be 16-byte aligned");
+    if (n_tris >= (1u << 26)) return fail(RT_ERR_ARG, "rt_set_triangles_device: 2^26 or more triangles");
+    if (n_mats >= (1u << 28)) return fail(RT_ERR_ARG, "rt_set_triangles_device: more than 2^28 materials");
+    if (n_mats && !mats32) return fail(RT_ERR_ARG, "rt_set_triangles_device: null materials");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    const std::vector<hrt_dev::MatDev> md = pack_materials(mats32, n_mats);
+    const size_t n = n_tris, n1 = std::max<size_t>(n, 1);
+    int rc = ensure(r->lb_tris, n1);
+    if (!rc) rc = ensure(r->lb_geo, 9 * n1);
+    if (!rc) rc = ensure(r->lb_mats, std::max<uint32_t>(n_mats, 1));
+    if (!rc) rc = ensure(r->lb_hnodes, 2 * std::max<size_t>(n1 - 1, 1));
+    if (!rc) rc = ensure(r->lb_order, n1);
+    if (!rc) rc = ensure(r->lb_stat, hrt_lbvh::STAT_WORDS);
+    if (rc) return rc;
+    uint64_t stat[hrt_lbvh::STAT_WORDS] = {};
+    if (n) {
+        const size_t tiles = (n + RT_REGROUP_TILE - 1u) / RT_REGROUP_TILE;
+        rc = ensure(r->lb_keys, 2 * n);
+        if (!rc) rc = ensure(r->lb_parent, 2 * n);
+        if (!rc) rc = ensure(r->lb_arrivals, n);
+        if (!rc) rc = ensure(r->lb_boxes, 2 * n * hrt_lbvh::BOX_WORDS);
+        if (!rc) rc = ensure(r->regroup_entries, 4u * n);
+        if (!rc) rc = ensure(r->regroup_counts, 256u * tiles + hrt_regroup::TAIL_WORDS);
+        if (rc) return rc;
+        hrt_lbvh::Launch a{};
+        a.tris64 = tris64_dev;
+        a.n = n_tris;
+        a.n_mats = n_mats;
+        a.tris_out = r->lb_tris.ptr;
+        a.geo_out = r->lb_geo.ptr;
+        a.hnodes = (hrt_lbvh::U4*)r->lb_hnodes.ptr;
+        a.order = r->lb_order.ptr;
+        a.keys = r->lb_keys.ptr;
+        a.keys_sorted = r->lb_keys.ptr + n;
+        a.parent = r->lb_parent.ptr;
+        a.arrivals = r->lb_arrivals.ptr;
+        a.boxes = r->lb_boxes.ptr;
+        a.stat = r->lb_stat.ptr;
+        a.sort_entries = r->regroup_entries.ptr;
+        a.sort_counts = r->regroup_counts.ptr;
+        HIP_TRY(hrt_launch_lbvh(a, r->stream));
+        HIP_TRY(hipMemcpyAsync(stat, r->lb_stat.ptr, sizeof stat, hipMemcpyDeviceToHost, r->stream));
+    }
+    if (n_mats)
+        HIP_TRY(hipMemcpyAsync(r->lb_mats.ptr, md.data(), (size_t)n_mats * sizeof(md[0]), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (stat[7] != 0) return fail(RT_ERR_ARG, "rt_set_triangles_device: triangle material index out of range");
+    const uint32_t finite = (uint32_t)stat[6];
+    if (finite > n_tris) return fail(RT_ERR_DEVICE, "rt_set_triangles_device: the build's status block is not consistent");
+    hrt::TriBvh T;
+    T.root_word = hrt_lbvh::root_word(finite);
+    T.depth = (uint32_t)stat[8];
+    if (finite) {
+        double lo[3], hi[3];
+        for (int k = 0; k < 3; k++) {
+            lo[k] = hrt_lbvh::f64_from_key(~stat[k]);
+            hi[k] = hrt_lbvh::f64_from_key(stat[3 + k]);
+        }
+        hrt_lbvh::root_sphere(lo, hi, T.root_center, &T.root_radius);
+    }
+    swap_buffers(r->tris, r->lb_tris);
+    swap_buffers(r->tri_geo, r->lb_geo);
+    swap_buffers(r->mats, r->lb_mats);
+    swap_buffers(r->tb_hnodes, r->lb_hnodes);
+    swap_buffers(r->tb_order, r->lb_order);
+    r->tri_tree = std::move(T);
+    r->tb_n_nodes = hrt_lbvh::node_slots(finite);
+    r->tb_n_order = finite;
+    r->tri_tree_dirty = false;
+    r->dev_geom = true;
+    r->bvh_n = 0;  // no reference heap: nothing reads one in this state (scene_params: tri_bvh)
+    r->bvh_m = n_tris;
+    r->so_ok = false;
+    r->nodes.release();
+    r->nodes_so.release();
+    std::vector<float>().swap(r->tri_aee);
+    r->cost_learn = true;
+    return RT_OK;
+}
+
+// The builder on the host (rt_lbvh.hpp host_build): pure CPU, no device.
+int rt_host_lbvh_build(const void* tris64, uint32_t n_tris, void* hnodes_out, size_t hnode_cap, uint32_t* order_out,
+                       size_t order_cap, uint32_t info[8], float root[4]) {
+    if (!info || !root) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null info or root");
+    if (n_tris && !tris64) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null triangles");
+    if (n_tris >= (1u << 26)) return fail(RT_ERR_ARG, "rt_host_lbvh_build: 2^26 or more triangles");
+    std::vector<float> aee(9 * (size_t)n_tris);
+    for (uint32_t j = 0; j < n_tris; j++) {
+        hrt::Triangle t;  // (no alignment asked of the caller)
+        std::memcpy(&t, (const char*)tris64 + 64u * (size_t)j, sizeof t);
+        const float v[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z,
+                            t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
+        std::copy(v, v + 9, &aee[9 * (size_t)j]);
+    }
+    const hrt_lbvh::HostTree T = hrt_lbvh::host_build(aee.data(), n_tris);
+    const size_t nodes = T.hnodes.size() / 2;
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, 0u, 0u, 0u};
+    std::copy(i8, i8 + 8, info);
+    for (int k = 0; k < 3; k++) root[k] = T.rc[k];
+    root[3] = T.radius;
+    if (hnode_cap == 0 && order_cap == 0) return RT_OK;
+    if (hnode_cap < nodes || order_cap < T.order.size()) return fail(RT_ERR_ARG, "rt_host_lbvh_build: a capacity is too small");
+    if ((nodes && !hnodes_out) || (!T.order.empty() && !order_out)) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null output");
+    if (nodes) std::memcpy(hnodes_out, T.hnodes.data(), nodes * 32u);
+    if (!T.order.empty()) std::memcpy(order_out, T.order.data(), T.order.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+int rt_testing_get_tri_tree(rt_renderer* r, void* hnodes_out, size_t hnode_cap, uint32_t* order_out, size_t order_cap,
+                            uint32_t info[8], float root[4]) {
+    if (!r || !info || !root) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: the sphere program has no triangle tree");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
+    const hrt::TriBvh& T = r->tri_tree;
+    const size_t nodes = r->tb_n_nodes, leaves = r->tb_n_order;
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)leaves, (uint32_t)leaves, T.root_word, T.depth, 0u, 0u, 0u};
+    std::copy(i8, i8 + 8, info);
+    for (int k = 0; k < 3; k++) root[k] = T.root_center[k];
+    root[3] = T.root_radius;
+    if (hnode_cap == 0 && order_cap == 0) return RT_OK;
+    if (hnode_cap < nodes || order_cap < leaves) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: a capacity is too small");
+    if ((nodes && !hnodes_out) || (leaves && !order_out)) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: null output");
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (nodes) HIP_TRY(hipMemcpy(hnodes_out, r->tb_hnodes.ptr, nodes * 32u, hipMemcpyDeviceToHost));
+    if (leaves) HIP_TRY(hipMemcpy(order_out, r->tb_order.ptr, leaves * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1625,6 +1792,17 @@ int rt_release_scratch(rt_renderer* r) {
     r->ring_ctl.release();
     r->regroup_entries.release();
     r->regroup_counts.release();
+    // rt_set_triangles_device's scratch and staging (the geometry before the last build), not the tree in use
+    r->lb_tris.release();
+    r->lb_geo.release();
+    r->lb_mats.release();
+    r->lb_hnodes.release();
+    r->lb_order.release();
+    r->lb_keys.release();
+    r->lb_parent.release();
+    r->lb_arrivals.release();
+    r->lb_boxes.release();
+    r->lb_stat.release();
     return RT_OK;
 }
 

@@ -162,6 +162,8 @@ SIGNATURES = {
     "rt_bounce_rays": (C.c_int, [_P, C.POINTER(RtBounce), _U32]),
     "rt_regroup_paths": (C.c_int, [_P, C.POINTER(RtRegroup), _U32]),
     "rt_host_regroup_keys": (C.c_int, [_PF, _PF, _U32, _PF, _PF, _PU32]),
+    "rt_set_triangles_device": (C.c_int, [_P, _P, _U32, _P, _U32]),
+    "rt_host_lbvh_build": (C.c_int, [_P, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),
@@ -210,6 +212,7 @@ TESTING_SIGNATURES = {
     "rt_testing_set_trace_rays_per_lane": (C.c_int, [_P, _U32]),
     "rt_testing_sphere_bvh_leaves": (C.c_int, [C.POINTER(C.c_float), _U32, C.POINTER(_U32), _U32,
                                                C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
+    "rt_testing_get_tri_tree": (C.c_int, [_P, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
 }
 
 _lib = None

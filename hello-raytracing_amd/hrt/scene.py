@@ -337,6 +337,35 @@ class Renderer:
         check(lib().rt_set_bvh(self._h, sz, nodes.ctypes.data, len(nodes), triangles.ctypes.data, len(triangles),
                                materials.ctypes.data, len(materials)), "write_buffer(bvh)")
 
+    def set_triangles_device(self, tris, materials: np.ndarray) -> None:
+        """rt_set_triangles_device: triangles from a contiguous torch tensor on the renderer's device, (m, 16) float32 or
+        (m, 64) uint8 in the layout of TRIANGLE_DTYPE, with an LBVH built for them on the GPU; materials as in write_bvh
+        (numpy). The renderer then has device geometry: every draw and query walks that tree (include/hrt.h).
+        Synchronises torch's current stream before the call; the call itself is synchronous."""
+        import torch
+
+        dev = self._torch_device()
+        if not torch.is_tensor(tris):
+            raise TypeError("set_triangles_device: tris must be a torch tensor on the renderer's device")
+        if tris.device != dev:
+            raise ValueError(f"set_triangles_device: tris is on {tris.device}, the renderer draws on {dev}")
+        if not ((tris.dtype == torch.float32 and tris.ndim == 2 and tris.shape[1] == 16) or
+                (tris.dtype == torch.uint8 and tris.ndim == 2 and tris.shape[1] == 64)):
+            raise ValueError(f"set_triangles_device: tris must be (m, 16) float32 or (m, 64) uint8, got "
+                             f"{tuple(tris.shape)} {tris.dtype}")
+        if not tris.is_contiguous():
+            raise ValueError("set_triangles_device: tris must be contiguous")
+        materials = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().rt_set_triangles_device(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0]),
+                                            materials.ctypes.data, len(materials)), "set_triangles_device")
+
+    def tri_tree(self) -> dict:
+        """Test-only (include/hrt_testing.h rt_testing_get_tri_tree): the triangle tree the renderer walks, read back, in
+        the format of hrt.lbvh_build."""
+        h = self._h
+        return _tree_dict(lambda *a: lib().rt_testing_get_tri_tree(h, *a), "testing_get_tri_tree")
+
     # --- knobs beyond the reference (WGSL compile-time constants there)
     @property
     def params(self) -> RtParams:
@@ -765,6 +794,31 @@ class Renderer:
         self.close()
 
 
+def _tree_dict(call, where: str) -> dict:
+    """The two-call protocol of rt_host_lbvh_build / rt_testing_get_tri_tree (sizes, then the arrays)."""
+    info, root = (C.c_uint32 * 8)(), (C.c_float * 4)()
+    check(call(None, 0, None, 0, info, root), where)
+    nodes = np.zeros((int(info[0]), 8), dtype=np.uint32)
+    order = np.zeros((int(info[1]),), dtype=np.uint32)
+    if nodes.size or order.size:
+        check(call(nodes.ctypes.data if nodes.size else None, len(nodes),
+                   order.ctypes.data_as(_lib._PU32) if order.size else None, len(order), info, root), where)
+    return {"nodes": nodes, "order": order, "info": np.array(list(info), dtype=np.uint32),
+            "root": np.array(list(root), dtype=np.float32)}
+
+
+def lbvh_build(triangles: np.ndarray) -> dict:
+    """rt_host_lbvh_build (include/hrt.h): rt_set_triangles_device's builder on the host, no device. triangles:
+    TRIANGLE_DTYPE records (or (m, 16) float32). Returns nodes (slots, 8) uint32 — per child [min | max << 16] fp16 bounds
+    per axis relative to the root centre, then the child word —, order (the finite triangles' indices in key order), info
+    {node slots, leaf positions, finite triangles, root word, depth, 0, 0, 0} and root (centre xyz, radius)."""
+    t = np.ascontiguousarray(triangles)
+    if t.dtype != TRIANGLE_DTYPE:
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 16)
+    m, p = len(t), t.ctypes.data
+    return _tree_dict(lambda *a: lib().rt_host_lbvh_build(p if m else None, m, *a), "rt_host_lbvh_build")
+
+
 def render_ppm(renderer: Renderer) -> str:
     """src/scene/render_ppm.rs:38-57 — blocking readback + ASCII P3."""
     return ppm_from_image(renderer.read_image(), renderer.width, renderer.height)
@@ -927,9 +981,22 @@ class SceneTris:
         sizes, nodes, tris, mats = self.tris_bvh.view()
         self.renderer.write_bvh(sizes, nodes[:MAX_TRIS], tris[:MAX_TRIS], mats[:MAX_MATS])
 
-    def init(self) -> None:
+    def write_triangles_device(self) -> None:
+        """The same triangles and materials through rt_set_triangles_device: uploaded as a torch tensor, the tree built on
+        the GPU (no reference heap: the renderer walks the device tree, include/hrt.h)."""
+        import torch
+
+        _, _, tris, mats = self.tris_bvh.view()
+        raw = np.ascontiguousarray(tris[:MAX_TRIS]).view(np.uint8).reshape(-1, 64)
+        self.renderer.set_triangles_device(torch.from_numpy(raw.copy()).to(self.renderer._torch_device()),
+                                           mats[:MAX_MATS])
+
+    def init(self, device_geometry: bool = False) -> None:
         self.renderer.set_camera(self.camera)
-        self.write_tree_data()
+        if device_geometry:
+            self.write_triangles_device()
+        else:
+            self.write_tree_data()
 
     def draw(self) -> None:
         self.renderer.draw()

@@ -84,7 +84,10 @@ typedef struct rt_params {
     uint32_t tri_bvh;          /* triangle program: 0 the reference's implicit-heap walk (default,
                                   parity), 1 opt-in binned-SAH tree with an ordered culling walk — the
                                   same closest hit except where the reference's 600-step cap or
-                                  unpadded slab tests drop a triangle (non-parity)  */
+                                  unpadded slab tests drop a triangle (non-parity).
+                                  Not read after rt_set_triangles_device: a renderer with device geometry
+                                  has no heap and walks its device-built tree with the kernels of 1,
+                                  until rt_set_bvh gives it a heap again                             */
     uint32_t suspend_below;    /* sample queue: a wave suspends its walks (sphere culling BVH of the sphere
                                   program; reference heap walk of the triangle / mixed programs) once
                                   fewer than this many of its 64 lanes are still walking, so finished
@@ -201,6 +204,40 @@ int rt_set_spheres(rt_renderer *r, const void *spheres48, uint32_t n);
 int rt_set_bvh(rt_renderer *r, const uint32_t sizes[2], const void *nodes32, uint32_t n_nodes,
                const void *tris64, uint32_t n_tris, const void *mats32, uint32_t n_mats);
 #define RT_MAX_TREE_NODES (1u << 26) /* 2^26 nodes (2 GiB), up to 2^26 - 1 triangles (4 GiB)            */
+
+/* ---- device geometry (no reference counterpart: the reference builds its tree on CPU threads) ----
+ * Triangles the caller keeps in device memory, for the triangle and mixed programs: n_tris Triangle records of 64 B, in
+ * the layout rt_set_bvh takes, in device memory on the renderer's GPU, 16-byte aligned; n_mats Material records in HOST
+ * memory, processed as rt_set_bvh processes them. The call makes the kernels' triangle records, builds an LBVH over the
+ * triangles on the GPU, in the node format of the tri_bvh = 1 walk, and leaves the renderer in a device-geometry state:
+ * it holds the triangles and that tree and no reference heap, and every draw and every query runs the kernels of
+ * tri_bvh = 1 whatever rt_params.tri_bvh says (rt_set_params rebuilds nothing). rt_set_bvh leaves the state. The hit
+ * contract is the one of tri_bvh = 1: the closest hit is the (t, triangle index) lexicographic minimum with the
+ * reference's Moller-Trumbore arithmetic, and rt_hit.prim is the index into the caller's array.
+ * The builder (csrc/rt_lbvh.hpp has every rule, DESIGN.md §7d the reasons): e1 = b - a, e2 = c - a in f32; f64 boxes over
+ * a, a + e1, a + e2; a triangle with a non-finite vertex stays out of the tree; 30-bit Morton keys of the f64 centroids
+ * in the root box; a stable sort; Karras' topology with index tie-break; children of at most 4 triangles become leaves;
+ * boxes fitted bottom-up in f64 and packed outward to fp16. The tree is a pure function of the triangle array:
+ * rt_host_lbvh_build gives the same bytes on the host.
+ * The call copies what it needs (the caller may overwrite tris64_dev after it returns) and is synchronous on the
+ * renderer's stream, like rt_set_bvh: it ends by reading a small status block back. The caller must have finished
+ * writing the triangles (the Python wrapper synchronises torch's current stream first).
+ * RT_ERR_ARG: the sphere program; a null tris64_dev with n_tris > 0; a pointer that is not 16-byte aligned;
+ * n_tris >= 2^26 or n_mats >= 2^28; a null mats32 with n_mats > 0; any triangle whose material >= n_mats (counted on the
+ * device). On any failure the renderer keeps the geometry it had: the build works in staging buffers that are swapped in
+ * on success. Those and the build's scratch count in rt_stats.device_bytes; rt_release_scratch frees them, not the tree.
+ * The image, the frame count and rt_get_stats are not touched; the learnt cost order is dropped, as by rt_set_bvh. */
+int rt_set_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_tris, const void *mats32,
+                            uint32_t n_mats);
+/* The same builder on the host, for n_tris Triangle records in host memory: pure CPU, no device, usable without a GPU,
+ * and what the tests compare the device tree with. hnodes_out: 32 B per node slot (per child six fp16 box bounds relative
+ * to the root centre, [min | max << 16] per axis, then the child word: a node index, or
+ * 0x80000000 | first << 4 | count for a leaf of `count` entries of order_out from `first`); slots no child word names
+ * are zero. order_out: the finite triangles' indices in key order. Capacities in node slots and in words.
+ * info: {node slots, leaf positions, finite triangles, root word, depth, 0, 0, 0}; root: {centre xyz, radius}; both are
+ * always written. With both capacities 0 only they are returned; a capacity that is too small otherwise is RT_ERR_ARG. */
+int rt_host_lbvh_build(const void *tris64, uint32_t n_tris, void *hnodes_out, size_t hnode_cap, uint32_t *order_out,
+                       size_t order_cap, uint32_t info[8], float root[4]);
 
 /* Renderer::set_time / set_frame_count — renderer.rs:315-323. */
 int rt_set_time(rt_renderer *r, uint32_t time);
@@ -489,8 +526,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
                              rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, then rt_regroup_paths /
-                             rt_host_regroup_keys, came later without a new version (no struct changed): detect them by
-                             their symbols */
+                             rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, came later without a
+                             new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

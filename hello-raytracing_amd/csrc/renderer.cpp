@@ -596,6 +596,8 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     P.bvh_rr_h = std::nextafter(B.root_radius * (1.0f + 0x1p-9f), INFINITY);
     P.bvh_nnodes = (uint32_t)B.nodes.size();
     // (the large list in LDS too: LLARGE_CAP; the leaf spheres: a leaf word in a 16-bit walk-stack entry)
+    // (bvh_walk_noovf's paired leaf pass is written out for leaves of at most hrt_dev::BVH_MAX_LEAF spheres)
+    static_assert(hrt::BVH_MAX_LEAF == hrt_dev::BVH_MAX_LEAF, "the builder's leaf size is the kernels'");
     P.bvh_lnodes = (B.nodes.size() <= hrt_dev::LNODE_CAP && B.depth <= hrt_dev::LNODE_DEPTH &&
                     B.large.size() <= hrt_dev::LLARGE_CAP && B.slot.size() <= hrt_dev::LNODE_LEAF_SPHERES) ? 1u : 0u;
     // (0 auto = off: the packet walk measured -8 % on C3)

@@ -452,6 +452,8 @@ int upload_spheres(rt_renderer* r) {
     for (const int sl : B.slot) caux.push_back(aux[(size_t)sl]);
     for (const int sl : B.large) caux.push_back(aux[(size_t)sl]);
     caux.insert(caux.end(), aux.begin(), aux.end());
+    // (k_trace_split reads the table through a buffer descriptor: a 32-bit range, KParams::code_aux_bytes)
+    if (caux.size() * sizeof(caux[0]) > 0xFFFFFFFFull) return fail(RT_ERR_ARG, "too many sphere slots for the hit-record table");
     int rc = ensure(r->sph_geo, nslots);
     if (!rc) rc = ensure(r->sph_aux, nslots);
     if (!rc) rc = ensure(r->code_aux, std::max<size_t>(caux.size(), 1));
@@ -615,6 +617,10 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
     P.bq_k2 = P.pad_k2;
     P.bq_k3 = P.pad_k3;
     P.bq_k4 = P.pad_k4;
+    // code_aux's records: the BVH codes, the large list, then every slot (upload_spheres bounds the size)
+    P.code_aux_bytes = r->code_aux.ptr == nullptr
+                           ? 0u
+                           : (uint32_t)((B.slot.size() + B.large.size() + (size_t)r->n_spheres) * sizeof(hrt_dev::SphereAux));
     return RT_OK;
 }
 
@@ -729,6 +735,10 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         if (!P.ring_mode) {
             r->ring.release();  // the other fold's memory: the draw's colour memory stays within the budget
             r->ring_ctl.release();
+            // k_trace_split carries a sample's index in the launch's buffer in 32 bits (KParams::sample_npix): a launch holds
+            // fewer than 2^32 samples (48 GiB of colours; the automatic budget stays below it)
+            const uint64_t idx_fit = 0xFFFFFFFFull / ((uint64_t)ntiles * 64u);
+            if (chunk > idx_fit) chunk = balanced((size_t)idx_fit);
             // a device short of memory gets smaller launches, down to one frame, instead of a failed draw
             const size_t buf_budget = std::max(budget, frame_bytes);
             while ((rc = ensure_within(r->samples, (size_t)chunk * frame_floats, buf_budget, fail_above)) == RT_ERR_ALLOC &&
@@ -920,6 +930,9 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
             // (a launch that steals still learns, so the next one can deal in cost order instead)
             const bool learn = want_order && (r->cost_learn || r->params.cost_order == 3u);
             P.tile_cost = learn ? r->tile_cost.ptr : nullptr;
+            P.sample_npix = ntiles * 64u;
+            if (!P.ring_mode && (uint64_t)P.nframes * P.sample_npix > 0xFFFFFFFFull)  // (the launch's sizing above)
+                return fail(RT_ERR_STATE, "a sample-buffer launch of 2^32 samples or more");
             HIP_TRY(hrt_launch_trace(r->mode, variant, P, r->stream));
             HIP_TRY(hipEventRecord(r->ev_trace[2 * r->trace_pairs_pending + 1], r->stream));
             r->trace_pairs_pending++;
@@ -1456,6 +1469,18 @@ int rt_testing_set_faults(rt_renderer* r, uint32_t ring_slots_max, uint32_t fail
     if (!r) return fail(RT_ERR_ARG, "rt_testing_set_faults: null");
     r->test_ring_slots_max = ring_slots_max;
     r->test_fail_alloc_above_mb = fail_alloc_above_mb;
+    return RT_OK;
+}
+
+int rt_testing_get_tile_order(rt_renderer* r, uint32_t* sum_out, uint32_t* order_out, size_t cap, size_t* count) {
+    if (!r || !count) return fail(RT_ERR_ARG, "rt_testing_get_tile_order: null");
+    const size_t n = r->order_tiles;
+    *count = n;
+    if (cap == 0u || n == 0u) return RT_OK;
+    if (cap < n || !sum_out || !order_out) return fail(RT_ERR_ARG, "rt_testing_get_tile_order: the capacity is too small");
+    HIP_TRY(hipMemcpyAsync(sum_out, r->tile_sum.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(order_out, r->tile_order.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }
 

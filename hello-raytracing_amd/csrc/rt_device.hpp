@@ -217,6 +217,10 @@ struct KParams {
     float bq_rr_h;
     float bq_k1, bq_k2, bq_k3, bq_k4;
     uint32_t bq_pad[3];
+    // the sample-buffer k_trace_split without stealing and packets (rt_kernels.hip trace_split, SEAMS):
+    uint32_t code_aux_bytes;      // size of code_aux, both tables (buffer-descriptor range; < 2^32: upload_spheres)
+    uint32_t sample_npix;         // tile-padded pixels of a frame, tiles_w * tiles_h * 64: a sample's index in the launch's
+                                  // buffer is frame * sample_npix + tile * 64 + pixel (< 2^32: launch_frames sizes the launch)
 };
 
 // The caller's buffers of one path step (rt_bounce_rays, include/hrt.h rt_bounce), typed: k_bounce_rays' second argument.

@@ -919,6 +919,30 @@ template <bool U = false>
 __device__ __forceinline__ void sphere_record(const KParams& P, const Ray& r, int bi, float t, Hit& h) {
     sphere_record_p<U>(P, point_on_ray(r.o, r.d, t), r.d, bi, t, h);
 }
+// sphere_record_p<true> with the record read through a buffer resource over KParams::code_aux (the sample-buffer
+// k_trace_split without stealing and packets): record bi at byte offset bi << 6, its fields at constant offsets of
+// that one 32-bit value, so no 64-bit address is formed or kept (as the leaf loads, leaf_sphere_test<FAST>). Returns
+// the offset: bytes 32..47 are one aligned group, id and the three DielConsts of scatter's dielectric arm (DielRegs).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ int sphere_record_rs(const __amdgpu_buffer_rsrc_t rs, const f3 p, const f3 d, int bi, float t,
+                                                Hit& h) {
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const int off = (int)((uint32_t)bi << 6);
+    const f4v g = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);       // cx, cy, cz, radius
+    const float inv_radius = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 48, 0));
+    const f4v a = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 16, 0);      // albedo, param
+    const uint32_t id = __builtin_amdgcn_raw_buffer_load_b32(rs, off, 32, 0);
+    f3 n = div_by_radius3_u(p - mk(g.x, g.y, g.z), g.w, inv_radius);
+    const bool front = dot(d, n) < 0.0f;
+    if (!front) n = -n;
+    h.p = p;
+    h.n = n;
+    h.t = t;
+    h.ar = a.x; h.ag = a.y; h.ab = a.z; h.param = a.w;
+    h.id = ((uint32_t)bi << 3) | 4u | (id == 1u || id == 2u ? id : 0u);
+    h.front = front;
+    return off;
+}
 
 // Coherent primary rays walked as one packet (k_trace_split<.., PACKET>). The 64 primary rays of
 // a frame block (one frame of one 8x8 tile) are nearly parallel: the union of the nodes their own walks visit is
@@ -1507,9 +1531,20 @@ __device__ __forceinline__ f3 random_on_hemisphere(uint32_t& s, const f3& n) {
 // The three material arms share code so a wave holding several materials runs one hemisphere sample and
 // one final normalize instead of one per arm; every lane still performs exactly its own arm's operations
 // (and RNG draws) in the reference's order, so results are unchanged.
-template <int MODE, bool U = false>  // U (sphere program): the exact sequences' guards as wave-uniform branches
-__device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, const Hit& h,
-                                        const SphereAux* __restrict__ tab = nullptr) {  // tab: as sphere_record_p
+// DC: where the dielectric arm's constants come from, made inside the arm (dcf()): DielMem, the hit's record in memory
+// (scatter below), or DielRegs, the group sphere_record_rs loaded with the record.
+struct DielMem {
+    const float* dc;  // &record.inv_param
+    __device__ __forceinline__ float inv_param() const { return dc[0]; }
+    __device__ __forceinline__ float r0sq(bool front) const { return front ? dc[1] : dc[2]; }
+};
+struct DielRegs {
+    float ip, rf, rb;
+    __device__ __forceinline__ float inv_param() const { return ip; }
+    __device__ __forceinline__ float r0sq(bool front) const { return front ? rf : rb; }
+};
+template <int MODE, bool U, typename DCF>  // U (sphere program): the exact sequences' guards as wave-uniform branches
+__device__ __forceinline__ void scatter_dc(uint32_t& s, Ray& r, const Hit& h, DCF dcf) {
     const bool lambert = (h.id & 3u) == 1u, metal = (h.id & 3u) == 2u;
     f3 hemi = mk(0.0f, 0.0f, 0.0f);
     if (lambert || metal) hemi = random_on_hemisphere<MODE>(s, h.n);  // 3 draws, both arms
@@ -1519,23 +1554,30 @@ __device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, c
         u = reflect(in, h.n) + h.param * hemi;
     } else if (!lambert) {  // MAT_DIELECTRIC and the default arm
         // ir = front ? 1 / param : param, and reflectance's r0 * r0 for that ir, from the host (DielConsts)
-        const SphereAux* __restrict__ aux = tab != nullptr ? tab : P.sph_aux;
-        const float* dc = (MODE == MODE_SPHERE || (MODE != MODE_TRIS && (h.id & 4u))) ? &aux[h.id >> 3].inv_param
-                                                                                     : &P.mats[h.id >> 3].inv_param;
-        const float ir = h.front ? dc[0] : h.param;
+        const auto dc = dcf();
+        const float ir = h.front ? dc.inv_param() : h.param;
         const float cos_t = fmin_ieee(dot(-r.d, h.n), 1.0f);
         const float sin_t = MODE == MODE_SPHERE ? (U ? sqrt_exact_u(1.0f - cos_t * cos_t) : sqrt_exact(1.0f - cos_t * cos_t))
                                                 : __builtin_sqrtf(1.0f - cos_t * cos_t);
         bool refl = ir * sin_t > 1.0f;  // cannot_refract; WGSL || short-circuits the RNG draw
         if (!refl) {
             const float f = rng_float(s);
-            refl = reflectance_r0sq(cos_t, h.front ? dc[1] : dc[2]) > (f - __builtin_floorf(f));
+            refl = reflectance_r0sq(cos_t, dc.r0sq(h.front)) > (f - __builtin_floorf(f));
         }
         u = refl ? reflect(r.d, h.n) : refract<MODE == MODE_SPHERE, U>(r.d, h.n, ir);
     }
     r.o = h.p;
     // (the triangle / mixed kernels keep the IEEE form: the fast one costs them spills)
     r.d = lambert ? hemi : (MODE == MODE_SPHERE ? (U ? normalize_exact_u(u) : normalize_exact(u)) : normalize(u));
+}
+template <int MODE, bool U = false>
+__device__ __forceinline__ void scatter(const KParams& P, uint32_t& s, Ray& r, const Hit& h,
+                                        const SphereAux* __restrict__ tab = nullptr) {  // tab: as sphere_record_p
+    scatter_dc<MODE, U>(s, r, h, [&]() {
+        const SphereAux* __restrict__ aux = tab != nullptr ? tab : P.sph_aux;
+        return DielMem{(MODE == MODE_SPHERE || (MODE != MODE_TRIS && (h.id & 4u))) ? &aux[h.id >> 3].inv_param
+                                                                                  : &P.mats[h.id >> 3].inv_param};
+    });
 }
 
 // (a, b) / sqrt(fma(b, b, a * a)) for two rng floats (each 0 or in [2^-32, 1]; the AA jitter and the disk direction
@@ -1715,8 +1757,6 @@ __device__ __forceinline__ LaneLists lane_lists() {
 // Hand-off form: MI355X_MICROARCH.md § visibility, row 1 of the sc1 table (the storing unit is the wave, which
 // drains before its atomic; the consumer learns by the value an atomic returned; every load of handed-off
 // bytes, slot or image, is an sc1 load).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ring_rsrc() {
@@ -3286,6 +3326,15 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     constexpr int SPLIT_STACK = LNODES ? (int)LNODE_DEPTH : 14;
     // (the packet kernels' block entries carry the winner's slot: they shade from the slot table)
     constexpr bool SHADE_BY_CODE = !PACKET;
+    // SEAMS: the round's code outside the walk, trimmed for the sample-buffer kernels without
+    // stealing and packets — the two the default schedule launches, uncounted and counting; the other instantiations keep
+    // their code and their register allocation. Four things, named where they stand: the winner's record through a
+    // buffer resource; one sample index per lane in place of (pixel, frame); the lane's "has a sample" in qs, a VGPR
+    // integer the phases compare directly, not a bool carried round the loop as a lane mask (QS_IDLE: no sample; QS_PASS:
+    // none, and passed over by this round's deal, which drew it a block entry outside the image; has() below); and no
+    // division by the row block in the refill of a renderer that owns every row.
+    constexpr bool SEAMS = !PACKET && !STEAL && !RING;
+    constexpr uint32_t QS_IDLE = 0xFFFFFFFFu, QS_PASS = 0xFFFFFFFEu;
     const uint32_t lane = threadIdx.x & 63u;
     constexpr bool STACK16 = split_stack16(LNODES, PACKET);
     static_assert(!STACK16 || (LNODE_CAP <= 0x8000u && (LNODE_CAP + 1u) * BVH_MAX_LEAF <= 2048u),
@@ -3322,7 +3371,10 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     float sky_t = 0.0f;
     uint32_t s = 0, bounce = 0, pix = 0, fl = 0;
     bool have = false;
-    uint32_t qs = 0;  // query state of the lane's sample: 0 start a query, 1 walking, 2 walk finished
+    uint32_t qs = SEAMS ? QS_IDLE : 0u;  // query state of the lane's sample: 0 start a query, 1 walking, 2 walk finished
+    // (SEAMS alone calls it; the others read `have`: one closure over both states, called by every instantiation, cost
+    // the stealing and packet kernels 2 to 9 spilled VGPRs, and so did a closure over `have` alone)
+    const auto has = [&]() { return (int)qs >= 0; };
     BvhQuery Q;
     // Primary rays are generated a frame-block at a time: when the wave's block (one frame of its job's
     // 8x8 tile) is used up, every lane computes the primary ray of its own pixel for the next frame at
@@ -3346,7 +3398,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     uint32_t nblocks = 0;
 #endif
     while (true) {
-        bool need = !have && !drained;
+        if constexpr (SEAMS) qs = (uint32_t)max((int)qs, (int)QS_IDLE);  // (passed over last round: idle again)
+        bool need = (SEAMS ? qs == QS_IDLE : !have) && !drained;
         unsigned long long m = __ballot(need);
         while (m != 0ull) {
             if (blk_next == 64u) {
@@ -3365,7 +3418,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                         blk_f++;
                     } else {
                         // (the tail: once this wave dealt a tail part, a new one only for CLAIM_FREE free lanes, as stealing)
-                        if ((J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE && __ballot(have) != 0ull)
+                        if ((J.get(WJ_FLAGS) & WJ_TAILPH) && (uint32_t)__popcll(m) < CLAIM_FREE &&
+                            __ballot(SEAMS ? has() : have) != 0ull)
                             break;
                         if (!job_acquire<FM, true>(J, lane, drained, job_tile, job_f0, job_nf)) break;
                         blk_f = 0;
@@ -3383,7 +3437,16 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 uint32_t ew = pok;  // entry word: bit 0 in the image, PACKET: bit 1 resolved, bit 2 hit, slot << 3
                 if (pok) {
                     const KPtr K = kargs();  // row map and time: loaded here, not held in SGPRs
-                    const uint32_t y = global_row(K->row0, K->row_block, K->row_stride, kr);
+                    uint32_t y;
+                    if constexpr (SEAMS) {
+                        // a renderer that owns every row (row_step 1: row_stride == row_block): local row kr is global row
+                        // row0 + kr, and the refill skips global_row's division by the block (a wave-uniform branch)
+                        const uint32_t rb = K->row_block, rs = K->row_stride;
+                        if (__builtin_expect(rb == rs, 1)) y = K->row0 + kr;
+                        else y = global_row(K->row0, rb, rs, kr);
+                    } else {
+                        y = global_row(K->row0, K->row_block, K->row_stride, kr);
+                    }
                     pr = primary_ray<MODE>(&K->cam, x, y, K->time0 + (job_f0 + blk_f) * K->dtime, ps);
                 }
                 blk[2 * threadIdx.x] = float4{pr.o.x, pr.o.y, pr.o.z, pr.d.x};
@@ -3445,18 +3508,25 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             const float ox = b0.x, oy = b0.y, oz = b0.z, dx = b0.w, dy = b1.x, dz = b1.y;
             const uint32_t ss = __float_as_uint(b1.z), ok = __float_as_uint(b1.w);
             bool took = false;
-            if (need && rank < avail) {
+            if ((SEAMS ? qs == QS_IDLE : need) && rank < avail) {
                 need = false;
+                if constexpr (SEAMS) qs = QS_PASS;
                 if (ok & 1u) {
                     ray.o = mk(ox, oy, oz);  // (PACKET, resolved hit: the hit point)
                     ray.d = mk(dx, dy, dz);
                     s = ss;
-                    fl = sample_ref<FM>(J, job_f0, blk_f);
-                    pix = job_tile * 64u + (uint32_t)src;
+                    if constexpr (SEAMS) {
+                        // one index per sample: frame of the launch x the frame's tile-padded pixels + the pixel, < 2^32
+                        // (renderer.cpp sizes the launch), in place of the pair the store multiplied out per sample
+                        pix = (job_f0 + blk_f) * kargs()->sample_npix + job_tile * 64u + (uint32_t)src;
+                    } else {
+                        fl = sample_ref<FM>(J, job_f0, blk_f);
+                        pix = job_tile * 64u + (uint32_t)src;
+                    }
                     sky_t = ray.d.y * 0.5f + 0.5f;
                     att = mk(1.0f, 1.0f, 1.0f);
                     bounce = 0;
-                    have = true;
+                    if constexpr (!SEAMS) have = true;
                     qs = 0;
                     if constexpr (PACKET) {
                         if (ok & 2u) {  // resolved by the packet: shade at once, the winner's slot (or -1) in Q.bc
@@ -3470,12 +3540,12 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             job_dealt<FM>(J, (uint32_t)__popcll(__ballot(took)));
             blk_next += min((uint32_t)__popcll(m), avail);
             if (blk_next == 64u && blk_f + 1u >= job_nf) job_close(J, lane);
-            m = __ballot(need);
+            m = __ballot(SEAMS ? qs == QS_IDLE : need);
         }
 #ifdef HRT_STAMPS
         wrec.drain(drained);
 #endif
-        if (__ballot(have) == 0ull) {
+        if (__ballot(SEAMS ? has() : have) == 0ull) {
             if (drained && J.idle()) break;
             if (!drained && idle_spin(J, lane)) break;  // nothing in flight: the next job waits for its ring slot
         }
@@ -3484,8 +3554,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         if (lane == 0) tally.rounds++;
 #endif
         HRT_PHASE(0);
-        HRT_LANES(0, have && qs == 0u);
-        if (have && qs == 0u) {
+        HRT_LANES(0, (SEAMS ? has() : have) && qs == 0u);
+        if (SEAMS ? qs == 0u : have && qs == 0u) {
             if (bounce < P.bounces) {
                 qs = bvh_begin<true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : 2u;
             } else {  // bounce cap 0: the sample is the sky colour
@@ -3493,8 +3563,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             }
         }
         HRT_PHASE(1);
-        HRT_LANES(1, have && qs == 1u);
-        if (have && qs == 1u) {
+        HRT_LANES(1, (SEAMS ? has() : have) && qs == 1u);
+        if (SEAMS ? qs == 1u : have && qs == 1u) {
             if constexpr (LNODES) {  // (depth <= LNODE_DEPTH = SPLIT_STACK: no overflow)
                 // (the leaf's first pass in pairs: not in the stealing kernels, which spilled 2 VGPRs with it)
                 constexpr bool PAIR = !PACKET && !STEAL;
@@ -3506,11 +3576,11 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             }
         }
         HRT_PHASE(2);
-        HRT_LANES(2, have && qs >= 2u);
+        HRT_LANES(2, (SEAMS ? has() : have) && qs >= 2u);
         // (PACKET: the queries shaded this round counted per wave — a wave-uniform count needs no VGPR; the others count
         // per lane, as before)
         if constexpr (PACKET) queries += (uint32_t)__popcll(__ballot(have && (qs == 2u || qs == 4u)));
-        if (have && qs >= 2u) {
+        if (SEAMS ? (int)qs >= 2 : have && qs >= 2u) {
 #ifdef HRT_STAMPS
             tally.lshade++;
             if (first_active_lane()) tally.wshade++;
@@ -3541,9 +3611,22 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 if constexpr (!PACKET) queries++;
                 if (bi >= 0) {
                     Hit h;
-                    const SphereAux* __restrict__ tab = SHADE_BY_CODE ? P.code_aux : nullptr;
-                    sphere_record_p<true>(P, p, ray.d, bi, best, h, tab);
-                    scatter<MODE, true>(P, s, ray, h, tab);  // (both: the guards as wave-uniform branches)
+                    if constexpr (SEAMS) {
+                        // (the record and the dielectric arm's constants through one resource over code_aux: both tables)
+                        const __amdgpu_buffer_rsrc_t rsa =
+                            __builtin_amdgcn_make_buffer_rsrc((void*)P.code_aux, (short)0, (int)P.code_aux_bytes, 0x00020000);
+                        // (the arm's three constants: one load of the record's bytes 32..47 inside the arm, at the offset the
+                        // record was read at — held from the record's loads to the arm, the group cost 16 B of scratch)
+                        const int aoff = sphere_record_rs(rsa, p, ray.d, bi, best, h);
+                        scatter_dc<MODE, true>(s, ray, h, [&]() {
+                            const u32x4 m = __builtin_amdgcn_raw_buffer_load_b128(rsa, aoff, 32, 0);
+                            return DielRegs{__uint_as_float(m.y), __uint_as_float(m.z), __uint_as_float(m.w)};
+                        });
+                    } else {
+                        const SphereAux* __restrict__ tab = SHADE_BY_CODE ? P.code_aux : nullptr;
+                        sphere_record_p<true>(P, p, ray.d, bi, best, h, tab);
+                        scatter<MODE, true>(P, s, ray, h, tab);  // (both: the guards as wave-uniform branches)
+                    }
                     att = att * mk(h.ar * 0.7f, h.ag * 0.7f, h.ab * 0.7f);
                     bounce++;
                     done = bounce >= P.bounces;
@@ -3553,11 +3636,28 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 const float u = 1.0f - sky_t;
                 const f3 sky = mk(0.54f * u + 0.54f * sky_t, 0.86f * u + 0.7f * sky_t, 0.92f * u + 0.98f * sky_t);
                 const f3 c = att * sky;
-                ring_store<FM>(J, pix, fl, c, bounce + 1u);
-                have = false;
+                if constexpr (SEAMS) {
+                    // (pix: the sample's index in the launch's buffer, formed when it was dealt — one 64-bit multiply-add)
+                    const KPtr RK = kargs();  // (the store's words: loaded here, not held in SGPRs)
+                    float* const o = RK->samples + (unsigned long long)pix * 3u;
+#if defined(HRT_STAMPS) && defined(HRT_DIAG_NOSTORE)  // (timing-only diagnostic build, as ring_store: wrong images)
+                    if (c.x == -12345.0f)
+#endif
+                    {
+                        o[0] = c.x;
+                        o[1] = c.y;
+                        o[2] = c.z;
+                    }
+                    // (a learning launch, cost-ordered dealing: the pixel's counter, ring_store; the pixel from the index)
+                    if (uint32_t* const tc = RK->tile_cost)
+                        __hip_atomic_fetch_add(tc + pix % RK->sample_npix, bounce + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    ring_store<FM>(J, pix, fl, c, bounce + 1u);
+                }
+                if constexpr (!SEAMS) have = false;
                 fin = true;
             }
-            qs = 0u;
+            qs = SEAMS && done ? QS_IDLE : 0u;
         }
         job_account<FM, 1>(J, fin, fl, lane);
         HRT_PHASE(3);

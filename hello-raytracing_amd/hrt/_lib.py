@@ -209,6 +209,7 @@ SIGNATURES = {
 TESTING_SIGNATURES = {
     "rt_testing_set_faults": (C.c_int, [_P, _U32, _U32]),
     "rt_testing_set_descent_hold": (C.c_int, [_P, _U32]),
+    "rt_testing_get_tile_order": (C.c_int, [_P, _PU32, _PU32, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_testing_set_trace_rays_per_lane": (C.c_int, [_P, _U32]),
     "rt_testing_sphere_bvh_leaves": (C.c_int, [C.POINTER(C.c_float), _U32, C.POINTER(_U32), _U32,
                                                C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),

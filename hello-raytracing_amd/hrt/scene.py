@@ -386,6 +386,17 @@ class Renderer:
         """Test-only fault injection (include/hrt_testing.h rt_testing_set_faults)."""
         check(lib().rt_testing_set_faults(self._h, ring_slots_max, fail_alloc_above_mb), "testing_set_faults")
 
+    def tile_order(self) -> tuple[np.ndarray, np.ndarray]:
+        """Test-only: what cost-ordered dealing has learnt, (per-tile cost sums, tile order), uint32[tiles] each
+        (include/hrt_testing.h rt_testing_get_tile_order)."""
+        n = C.c_size_t(0)
+        check(lib().rt_testing_get_tile_order(self._h, None, None, 0, C.byref(n)), "testing_get_tile_order")
+        sums, order = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(lib().rt_testing_get_tile_order(self._h, sums.ctypes.data_as(_lib._PU32), order.ctypes.data_as(_lib._PU32),
+                                                  n.value, C.byref(n)), "testing_get_tile_order")
+        return sums, order
+
     def set_descent_hold(self, hold: int) -> None:
         """Test-only: the descent hold of k_trace_split (include/hrt_testing.h rt_testing_set_descent_hold)."""
         check(lib().rt_testing_set_descent_hold(self._h, hold), "testing_set_descent_hold")

@@ -47,6 +47,13 @@ int rt_testing_sphere_bvh_leaves(const float *centers_radii, uint32_t n_slots, u
 int rt_testing_get_tri_tree(rt_renderer *r, void *hnodes_out, size_t hnode_cap, uint32_t *order_out, size_t order_cap,
                             uint32_t info[8], float root[4]);
 
+/* Blocking read-back of what cost-ordered dealing (rt_params.cost_order) has learnt: per tile (8x8 pixels, raster order
+ *   over the renderer's rows) the sum of its pixels' cost counters from the last learning launch — a finished sample adds
+ *   its bounces + 1 to its pixel — and the tile order built from the sums, a permutation of the tiles. count: the tiles
+ *   the renderer holds an order for (0 before the first learning launch), always written. With cap 0 only the count is
+ *   returned; a smaller cap otherwise is RT_ERR_ARG. */
+int rt_testing_get_tile_order(rt_renderer *r, uint32_t *sum_out, uint32_t *order_out, size_t cap, size_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include "rt_device.hpp"
 #include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
+#include "rt_tile_lists.hpp"
 
 hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_accumulate(const hrt_dev::KParams& P, hipStream_t stream);
@@ -43,6 +44,8 @@ hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hi
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
 uint32_t hrt_order_scratch_words(uint32_t ntiles);
+hipError_t hrt_launch_tile_lists(const hrt_tiles::View& V, const float4* bvh_sph, uint32_t nleaf, uint32_t* lists,
+                                 hipStream_t stream);
 const char* hrt_last_kernel();
 void hrt_reset_last_kernel();
 hipError_t hrt_check_exact_math(unsigned long long n, uint32_t seed, unsigned long long* out_dev, hipStream_t st);
@@ -228,6 +231,14 @@ struct rt_renderer {
     // cost_learn: the next sample-buffer launch learns (set by every scene, camera, size or parameter change)
     DevBuf<uint32_t> tile_cost, tile_sum, tile_order, order_scratch;
     uint32_t cost_tiles = 0, order_tiles = 0;
+    // the tiles' primary candidate lists (rt_tile_lists.hpp; KParams::tile_lists): built by the first draw that can use
+    // them and again whenever the view they were built for (camera, image, row share, K) or the sphere set differs;
+    // tile_list_mode / _k: hrt_testing.h (0 auto = on, 1 off, 2 on)
+    DevBuf<uint32_t> tile_lists;
+    hrt_tiles::View tile_view{};
+    bool tile_lists_valid = false;
+    unsigned long long blocks_resolved = 0;  // of the last draw whose statistics were read (finish_stats)
+    uint32_t tile_list_mode = 0, tile_list_k = hrt_tiles::K_MAX;
     bool cost_learn = true;
     uint32_t last_ordered = 0;  // trace launches of the last sample-queue draw that dealt in cost order
     DevBuf<unsigned long long> wave_trace;  // diagnostic build only
@@ -263,7 +274,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -487,6 +498,7 @@ int upload_spheres(rt_renderer* r) {
         HIP_TRY(hipStreamSynchronize(r->stream));  // host staging vectors die here
     }
     r->n_spheres = nslots;
+    r->tile_lists_valid = false;
     return RT_OK;
 }
 
@@ -622,6 +634,59 @@ int scene_params(rt_renderer* r, hrt_dev::KParams& P) {
                            ? 0u
                            : (uint32_t)((B.slot.size() + B.large.size() + (size_t)r->n_spheres) * sizeof(hrt_dev::SphereAux));
     return RT_OK;
+}
+
+// What the tile lists are a function of, besides the leaf spheres (rt_tile_lists.hpp): the camera constants and row share
+// of scene_params, 8x8 tiles over W x nrows, and K.
+hrt_tiles::View tile_view_of(const hrt_dev::KParams& P, uint32_t k_list) {
+    hrt_tiles::View V;
+    std::memset(&V, 0, sizeof V);  // (the padding too: views are compared as bytes)
+    for (int i = 0; i < 4; i++) {
+        V.eye[i] = P.cam.eye[i];
+        V.dir[i] = P.cam.dir[i];
+        V.up[i] = P.cam.up[i];
+        V.right[i] = P.cam.right[i];
+    }
+    V.focal = P.cam.focal;
+    V.blur = P.cam.blur;
+    V.k = P.cam.k;
+    V.aspect = P.cam.aspect;
+    V.wm1 = P.cam.wm1;
+    V.hm1 = P.cam.hm1;
+    V.W = P.W;
+    V.H = P.H;
+    V.row0 = P.row0;
+    V.row_block = P.row_block;
+    V.row_stride = P.row_stride;
+    V.nrows = P.nrows;
+    V.tiles_w = (P.W + 7u) / 8u;
+    V.tiles_h = (P.nrows + 7u) / 8u;
+    V.k_list = std::min(k_list, hrt_tiles::K_MAX);
+    return V;
+}
+
+// The lists for P's view, built on the device unless the renderer holds them already. A camera that moves rebuilds them
+// every draw: one thread per tile over the leaf spheres, no scratch (C3: 32,400 tiles x 483 spheres).
+int ensure_tile_lists(rt_renderer* r, const hrt_dev::KParams& P) {
+    const hrt_tiles::View V = tile_view_of(P, r->tile_list_k);
+    if (r->tile_lists_valid && std::memcmp(&V, &r->tile_view, sizeof V) == 0) return RT_OK;
+    r->tile_lists_valid = false;
+    const size_t ntiles = (size_t)V.tiles_w * V.tiles_h;
+    int rc = ensure(r->tile_lists, std::max<size_t>(ntiles * hrt_tiles::WORDS, 1));
+    if (rc) return rc;
+    HIP_TRY(hrt_launch_tile_lists(V, r->bvh_sph.ptr, P.bvh_nleaf, r->tile_lists.ptr, r->stream));
+    r->tile_view = V;
+    r->tile_lists_valid = true;
+    return RT_OK;
+}
+
+// k_trace_split<LNODES, false, false, false> answers a listed tile's primary rays when it makes their frame block
+// (rt_kernels.hip trace_split, BLOCKRES): the sphere program's culling walk with the nodes in LDS, the sample buffer, no
+// counting, no packets, a bounce cap of at least 1 (a launch that steals runs another kernel: launch_frames).
+bool tile_lists_wanted(const rt_renderer* r, const hrt_dev::KParams& P, int variant) {
+    return r->tile_list_mode != 1u && r->mode == RT_MODE_SPHERE && variant == hrt_dev::SCAN_BVH && P.bvh_lnodes && !P.packet &&
+           !P.count_tests && P.bounces >= 1u && P.bvh_nleaf > 0u &&
+           (uint64_t)P.bvh_nleaf + P.nlarge < hrt_dev::TILE_LIST_CODES;
 }
 
 int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime) {
@@ -855,6 +920,7 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
         r->last_suspend = split ? r->params.suspend_below : 0u;
         P.job_frames = jf;
         HIP_TRY(hipEventRecord(r->ev_start, r->stream));
+        const bool lists = split && !P.ring_mode && tile_lists_wanted(r, P, variant);
         P.fold_prev = nullptr;
         for (uint32_t done = 0, k = 0; done < count; done += chunk, k++) {
             if (fold_next) {
@@ -886,6 +952,16 @@ int launch_frames(rt_renderer* r, uint32_t count, uint32_t time0, uint32_t dtime
                 // (k_trace's frame-block refill for the linear sphere scan with the same stealing ran 3x slower, C2 80 ->
                 // 26 Grays/s: a claim per 64 cheap samples stalls the wave; profiles/r05/o/)
                 P.steal = (split && !P.ring_mode && fits && want) ? 1u : 0u;
+            }
+            // The tile lists, built by the first launch that reads them: a launch that steals runs another kernel, so a
+            // draw of short launches (a rank's share) never pays for lists. Inside the draw's timing, outside the launch's
+            // own pair of events: the first draw of a view shows their cost in its rt_stats, later draws find them built —
+            // bench.py's warmup pays for them, not every step.
+            P.tile_lists = nullptr;
+            if (lists && !P.steal) {
+                rc = ensure_tile_lists(r, P);
+                if (rc) return rc;
+                P.tile_lists = r->tile_lists.ptr;
             }
             // Tail split (the suspendable-walk kernels with the sample buffer, no stealing): the last ~2 jobs per
             // resident wave are dealt in parts (rt_params.tail_split: 2 quarters, 3 eighths; 0 auto = quarters),
@@ -995,6 +1071,8 @@ int finish_stats(rt_renderer* r) {
         HIP_TRY(hipMemcpy(sp.data(), r->count_spread.ptr, sp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (uint32_t k = 0; k < hrt_dev::CSPREAD; k++)
             for (uint32_t c = 0; c < 5u; c++) q[c] += sp[(size_t)k * hrt_dev::CSTRIDE + c];
+        r->blocks_resolved = 0;  // (word 5: the frame blocks resolved when made, rt_testing_get_tile_lists_resolved)
+        for (uint32_t k = 0; k < hrt_dev::CSPREAD; k++) r->blocks_resolved += sp[(size_t)k * hrt_dev::CSTRIDE + 5u];
     }
     HIP_TRY(hipMemcpy(wd, r->counter.ptr + hrt_dev::WATCHDOG, sizeof wd, hipMemcpyDeviceToHost));
     if (wd[0] || wd[3]) {  // waves gave up waiting for a fold-ring slot: the image is incomplete; report, do not hang
@@ -1087,6 +1165,8 @@ void delete_buffers(rt_renderer* r) {
     r->tile_cost.release();
     r->tile_sum.release();
     r->tile_order.release();
+    r->tile_lists.release();
+    r->tile_lists_valid = false;
     r->order_scratch.release();
     r->cost_tiles = r->order_tiles = 0;
 }
@@ -1488,6 +1568,93 @@ int rt_testing_set_descent_hold(rt_renderer* r, uint32_t hold) {
     if (hold > 64) return fail(RT_ERR_ARG, "rt_testing_set_descent_hold: hold must be 0..64");
     if (!r) return fail(RT_ERR_ARG, "rt_testing_set_descent_hold: null");
     r->descent_hold = hold;
+    return RT_OK;
+}
+
+int rt_testing_set_tile_lists(rt_renderer* r, uint32_t mode, uint32_t k) {
+    if (mode > 2u || k > hrt_tiles::K_MAX) return fail(RT_ERR_ARG, "rt_testing_set_tile_lists: mode must be 0..2 and k 0..8");
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_tile_lists: null");
+    r->tile_list_mode = mode;
+    r->tile_list_k = k;
+    return RT_OK;
+}
+
+int rt_testing_get_tile_lists_resolved(rt_renderer* r, uint64_t* blocks) {
+    if (!r || !blocks) return fail(RT_ERR_ARG, "rt_testing_get_tile_lists_resolved: null");
+    const int rc = finish_stats(r);
+    if (rc) return rc;
+    *blocks = r->blocks_resolved;
+    return RT_OK;
+}
+
+int rt_testing_get_tile_lists(rt_renderer* r, uint32_t* words_out, size_t cap, size_t* count) {
+    if (!r || !count) return fail(RT_ERR_ARG, "rt_testing_get_tile_lists: null");
+    if (r->mode != RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_testing_get_tile_lists: the sphere program only");
+    if (!r->has_camera) return fail(RT_ERR_STATE, "rt_set_camera must be called before rt_testing_get_tile_lists");
+    DeviceScope scope(r->device);
+    if (scope.rc) return scope.rc;
+    hrt_dev::KParams P{};
+    int rc = scene_params(r, P);
+    if (rc) return rc;
+    const hrt_tiles::View V = tile_view_of(P, r->tile_list_k);
+    const size_t n = (size_t)V.tiles_w * V.tiles_h * hrt_tiles::WORDS;
+    *count = n;
+    if (cap == 0) return RT_OK;
+    if (cap < n || !words_out) return fail(RT_ERR_ARG, "rt_testing_get_tile_lists: the capacity is too small");
+    if (n == 0) return RT_OK;
+    rc = ensure_tile_lists(r, P);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(words_out, r->tile_lists.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+int rt_host_tile_lists(const void* camera80, uint32_t width, uint32_t height, uint32_t row0, uint32_t row_step,
+                       uint32_t row_block, const void* spheres48, uint32_t n, uint32_t min_sphere_slots, uint32_t k,
+                       uint32_t* words_out, size_t cap, size_t* count) {
+    if (!camera80 || !count || (n && !spheres48)) return fail(RT_ERR_ARG, "rt_host_tile_lists: null");
+    if (width == 0 || height == 0 || row_step == 0 || k > hrt_tiles::K_MAX)
+        return fail(RT_ERR_ARG, "rt_host_tile_lists: width, height and row_step must be positive and k at most 8");
+    // the renderer's own steps: the slots and their culling BVH (upload_spheres), the camera constants (scene_params)
+    const hrt::Sphere* sp = (const hrt::Sphere*)spheres48;
+    const uint32_t nslots = std::max(n, min_sphere_slots);
+    std::vector<float> cr(4 * (size_t)nslots, 0.0f);
+    for (uint32_t i = 0; i < n; i++) {
+        cr[4 * i + 0] = sp[i].center.x;
+        cr[4 * i + 1] = sp[i].center.y;
+        cr[4 * i + 2] = sp[i].center.z;
+        cr[4 * i + 3] = sp[i].radius;
+    }
+    const hrt::SphereBvh B = hrt::build_sphere_bvh(cr);
+    hrt::Camera c;
+    std::memcpy(&c, camera80, sizeof c);
+    hrt_dev::KParams P{};
+    const float* cam = &c.eye.x;
+    for (int i = 0; i < 4; i++) {
+        P.cam.eye[i] = cam[i];
+        P.cam.dir[i] = cam[4 + i];
+        P.cam.up[i] = cam[8 + i];
+        P.cam.right[i] = cam[12 + i];
+    }
+    P.cam.focal = c.params.x;
+    P.cam.blur = c.params.y;
+    P.cam.k = std::tan(c.params.z * 0.5f);
+    P.cam.aspect = (float)width / (float)height;
+    P.cam.wm1 = (float)width - 1.0f;
+    P.cam.hm1 = (float)height - 1.0f;
+    P.W = width;
+    P.H = height;
+    P.row0 = row0;
+    P.row_block = std::max(row_block, 1u);
+    P.row_stride = row_step * P.row_block;
+    P.nrows = local_rows_of(height, row0, row_step, P.row_block);
+    const hrt_tiles::View V = tile_view_of(P, k);
+    const size_t ntiles = (size_t)V.tiles_w * V.tiles_h, words = ntiles * hrt_tiles::WORDS;
+    *count = words;
+    if (cap == 0) return RT_OK;
+    if (cap < words || !words_out) return fail(RT_ERR_ARG, "rt_host_tile_lists: the capacity is too small");
+    for (size_t t = 0; t < ntiles; t++)
+        hrt_tiles::tile_list(V, (uint32_t)t, B.sph.data(), (uint32_t)B.slot.size(), words_out + t * hrt_tiles::WORDS);
     return RT_OK;
 }
 

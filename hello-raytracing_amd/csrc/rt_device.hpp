@@ -97,6 +97,11 @@ constexpr uint32_t BVH_MAX_LEAF = 4;
 // kernel's 22,816 B + 224 B = 23,040 B, a multiple of the 512-B LDS allocation granule that still fits 7 workgroups in
 // the CU's 160 KB (16 entries round up to 23,552 B: the seventh workgroup no longer fits, C3 -2.6 %)
 constexpr uint32_t LLARGE_CAP = 14;
+// Per-tile primary candidate lists (rt_tile_lists.hpp; k_trace_split's block-time resolve): TILE_LIST_WORDS words per
+// 8x8 tile, the count (TILE_LIST_WALK: the tile's blocks walk their primary rays as ever) then up to TILE_LIST_K BVH
+// codes of leaf spheres. A frame-block entry of a resolved primary ray keeps the winner's code in 24 bits.
+constexpr uint32_t TILE_LIST_K = 8, TILE_LIST_WORDS = 1 + TILE_LIST_K, TILE_LIST_WALK = 0xFFFFFFFFu;
+constexpr uint32_t TILE_LIST_CODES = 1u << 24;
 
 // Camera-derived constants of make_ray / fs_main, read only when primary rays are generated (once per frame
 // block in the sample queue). The kernels read them through kargs() (below), a pointer to the kernarg segment
@@ -221,6 +226,9 @@ struct KParams {
     uint32_t code_aux_bytes;      // size of code_aux, both tables (buffer-descriptor range; < 2^32: upload_spheres)
     uint32_t sample_npix;         // tile-padded pixels of a frame, tiles_w * tiles_h * 64: a sample's index in the launch's
                                   // buffer is frame * sample_npix + tile * 64 + pixel (< 2^32: launch_frames sizes the launch)
+    // k_trace_split<true, false, false, false> (BLOCKRES): the tiles' primary candidate lists, TILE_LIST_WORDS words per tile
+    // of the renderer's rows (renderer.cpp ensure_tile_lists; null: none, every block walks its primary rays)
+    const uint32_t* tile_lists;
 };
 
 // The caller's buffers of one path step (rt_bounce_rays, include/hrt.h rt_bounce), typed: k_bounce_rays' second argument.

@@ -16,6 +16,7 @@
 //   * the implicit-heap BVH walk (shader_tris.wgsl:268-301) is per lane, with the reference's
 //     traversal order and 600-step cap.
 #include "rt_device.hpp"
+#include "rt_tile_lists.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -181,7 +182,11 @@ __device__ __forceinline__ int scan_spheres_deferred(const KParams& P, const Ray
 // Lane 0 of a wave, at its end: its work counts (queries, box / sphere tests, node / triangle tests) added to its copy of
 // the counters (wave id % CSPREAD). One set of counters for every wave made the launch's last ~1 ms a queue of
 // same-address atomics (C2: 6144 waves x 5).
-__device__ __forceinline__ void flush_counts(const unsigned long long (&sums)[5]) {
+// (N = 6, k_trace_split's block-resolving kernel: word 5, the frame blocks it resolved when it made them — read by
+// rt_testing_get_tile_lists_resolved alone)
+template <int N>
+__device__ __forceinline__ void flush_counts(const unsigned long long (&sums)[N]) {
+    static_assert(N >= 5 && N <= (int)CSTRIDE, "the counters' copies are CSTRIDE words apart");
 #if defined(HRT_STAMPS) && defined(HRT_DIAG_NOFLUSH)  // (timing-only diagnostic build: no work counters)
     if (sums[0] != ~0ull) return;
 #endif
@@ -192,7 +197,7 @@ __device__ __forceinline__ void flush_counts(const unsigned long long (&sums)[5]
     const uint32_t idx = (hw ^ (hw >> 8) ^ (hw >> 13) ^ blockIdx.x) & (CSPREAD - 1u);
     unsigned long long* const c = kargs()->count_spread + idx * CSTRIDE;
 #pragma unroll
-    for (int k = 0; k < 5; k++) atomicAdd(c + k, sums[k]);
+    for (int k = 0; k < N; k++) atomicAdd(c + k, sums[k]);
 }
 
 struct Tally {
@@ -3335,6 +3340,15 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     // division by the row block in the refill of a renderer that owns every row.
     constexpr bool SEAMS = !PACKET && !STEAL && !RING;
     constexpr uint32_t QS_IDLE = 0xFFFFFFFFu, QS_PASS = 0xFFFFFFFEu;
+    // BLOCKRES: the uncounted SEAMS kernel with the nodes in LDS answers and shades a listed tile's primary rays when its frame block is made
+    // (KParams::tile_lists; the refill below). The counting twins walk every primary ray, so their test counts stay what
+    // every other kernel form counts.
+    constexpr bool BLOCKRES = SEAMS && !COUNT && LNODES;
+    // (its register budget, 64 VGPRs without scratch beside the block-time code: the queries counted per wave, as PACKET;
+    // a lane's rank by mbcnt, no lane mask held; "the walk is left to the full scan" as a query state, QS_FULL, where
+    // the other kernels hold Q.full_scan — bvh_begin alone sets it here, the LDS-node walk does not overflow)
+    constexpr bool WAVEQ = PACKET || BLOCKRES;
+    constexpr uint32_t QS_FULL = 5u;
     const uint32_t lane = threadIdx.x & 63u;
     constexpr bool STACK16 = split_stack16(LNODES, PACKET);
     static_assert(!STACK16 || (LNODE_CAP <= 0x8000u && (LNODE_CAP + 1u) * BVH_MAX_LEAF <= 2048u),
@@ -3360,6 +3374,9 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         __syncthreads();
     }
     __shared__ float4 blk[2 * 256];  // the wave's frame block: (o.xyz, d.x), (d.yz, state bits, ok) per lane
+    // SEAMS, a block resolved when it was made (KParams::tile_lists, below): the entry's ninth word, the path's sky_t
+    __shared__ float blk_sky[BLOCKRES ? 256 : 1];
+    constexpr uint32_t EW_RES = 0x80000000u;  // entry word of such an entry: 1 | pixel of the tile << 1 | winner's code << 7 | EW_RES
     Tally tally;
     uint32_t queries = 0;
     // (one kernarg word: the suspend threshold in bits 0..7, the descent hold in bits 8..15 — renderer.cpp)
@@ -3381,6 +3398,12 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     // once (all lanes busy) into the wave's slice of `blk`, and lanes that need a sample read theirs from
     // it, instead of each freed lane computing its own with a few lanes active.
     uint32_t job_tile = 0, job_f0 = 0, job_nf = 0, blk_f = 0, blk_next = 64;  // wave-uniform
+    // SEAMS: the block's entries (wave-uniform), 64, or the scattered survivors of a block resolved when it was made
+    // (0: the block yields no entry, and the deal makes the next one)
+    uint32_t blk_cnt = 64;
+    uint32_t nres = 0;   // BLOCKRES: the blocks resolved when made, per wave (a test's observable; HRT_STAMPS: the tallies')
+    uint32_t nfull = 0;  // BLOCKRES: the queries left to the full scan, per wave (the uncounted kernels' only sphere tests)
+    const auto blk_n = [&]() { return BLOCKRES ? blk_cnt : 64u; };
     __shared__ uint32_t wjobs[4 * WJ_WORDS];
     // (the fold ring's launches fold nothing of the launch before: renderer.cpp's fold_next needs the sample buffer)
     // (the wave's words, the stack pointer and the lane mask after the fold, whose eight frames in flight take the
@@ -3402,7 +3425,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         bool need = (SEAMS ? qs == QS_IDLE : !have) && !drained;
         unsigned long long m = __ballot(need);
         while (m != 0ull) {
-            if (blk_next == 64u) {
+            if (blk_next == blk_n()) {
                 if constexpr (STEAL) {  // one frame block at a time, stolen once the queue is drained (steal_block)
                     if ((uint32_t)__popcll(m) < CLAIM_FREE && J.get(WJ_PRIV_N) == 0u && __ballot(have) != 0ull &&
                         queue_drained(J, lane))
@@ -3449,8 +3472,128 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                     }
                     pr = primary_ray<MODE>(&K->cam, x, y, K->time0 + (job_f0 + blk_f) * K->dtime, ps);
                 }
-                blk[2 * threadIdx.x] = float4{pr.o.x, pr.o.y, pr.o.z, pr.d.x};
-                blk[2 * threadIdx.x + 1] = float4{pr.d.y, pr.d.z, __uint_as_float(ps), __uint_as_float(ew)};
+                // SEAMS, a tile with a primary candidate list (KParams::tile_lists; rt_tile_lists.hpp: every leaf sphere a
+                // primary ray of the tile could be accepted by): the block's 64 primary queries are answered here, by all
+                // lanes at once — the large list and the tile's list with the leaf's own arithmetic, the (t, slot) minimum —
+                // a miss stores its sky colour, a hit scatters, and the block's entries are the scattered rays alone,
+                // compacted: a lane that takes one starts at its first secondary query. The same bits and the same
+                // query count as walking the ray: the walk accepts no sphere the list lacks.
+                bool resolved = false;  // (wave-uniform)
+                if constexpr (BLOCKRES) {
+                    typedef const __attribute__((address_space(4))) uint32_t* CU32;
+                    typedef float f4v __attribute__((ext_vector_type(4)));
+                    typedef const __attribute__((address_space(4))) f4v* CF4;
+                    blk_cnt = 64u;
+                    const KPtr TK = kargs();
+                    const CU32 tl = (CU32)TK->tile_lists + uniform(job_tile) * TILE_LIST_WORDS;
+                    const uint32_t ln = TK->tile_lists != nullptr ? tl[0] : TILE_LIST_WALK;
+                    const float a = dot(pr.d, pr.d);
+                    const float a4 = 4.0f * a, a2 = 2.0f * a;
+                    // (bvh_begin's rule: a ray the culling bound does not cover takes the full scan, so its block walks)
+                    const bool cov = (a2 > 0x1p-100f && a2 < 0x1p100f) && __builtin_isfinite(pr.o.x) &&
+                                     __builtin_isfinite(pr.o.y) && __builtin_isfinite(pr.o.z);
+                    if (ln != TILE_LIST_WALK && __ballot(pok != 0u && !cov) == 0ull) {
+                        resolved = true;
+                        nres++;
+                        // Nine words of the lane's own sample (a suspended walk's, or none) wait in the lane's entry of the
+                        // used-up block while the block is resolved and shaded: the kernel has no registers for both (its
+                        // 64-VGPR budget), and the entries are written only after the nine are back.
+                        blk[2 * threadIdx.x] = float4{ray.o.x, ray.o.y, ray.o.z, ray.d.x};
+                        blk[2 * threadIdx.x + 1] = float4{ray.d.y, ray.d.z, __uint_as_float(s), __uint_as_float(pix)};
+                        blk_sky[threadIdx.x] = sky_t;
+                        const bool live = pok != 0u;
+                        float bt = FLT_MAX_REF;
+                        int bc = -1;
+                        const uint32_t nleaf = P.bvh_nleaf, nlarge = TK->bq_nlarge;
+                        // (the large list as bvh_begin: ascending slots, an equal t later in the list never wins)
+                        for (uint32_t k = 0, n = LLDS ? min(nlarge, LLARGE_CAP) : nlarge; k < n; k++) {
+                            const float4 g = LLDS ? lgeo[k] : P.sph_geo[P.large_slots[k]];
+                            const bool cand = live && sphere_candidate(g, pr, a4);
+                            const float t = candidate_t(g, pr, a4, a2, cand);
+                            if (cand && t > 0.0f && t < bt) { bt = t; bc = (int)(nleaf + k); }
+                        }
+                        const CF4 sg = (CF4)P.bvh_sph;
+                        for (uint32_t k = 0; k < ln; k++) {
+                            const uint32_t code = tl[1u + k];
+                            const f4v gv = sg[code];
+                            const float4 g = float4{gv.x, gv.y, gv.z, gv.w};
+                            const bool cand = live && sphere_candidate(g, pr, a4);
+                            const float t = candidate_t(g, pr, a4, a2, cand);
+                            if (cand && t > 0.0f && t <= bt) {  // beats(): a tie needs both slots (rare)
+                                if (t < bt || (bc >= 0 && P.bvh_slot[code] < bvh_slot_of(P, bc))) { bt = t; bc = (int)code; }
+                            }
+                        }
+                        queries += (uint32_t)__popcll(__ballot(live));
+                        const bool hit = live && bc >= 0;
+#ifdef HRT_STAMPS  // (the diagnostic tallies: a resolved block's rays are shaded here, one shade event of the wave)
+                        if (live) tally.lshade++;
+                        if (lane == 0) tally.wshade++;
+#endif
+                        const float st = pr.d.y * 0.5f + 0.5f;
+                        f3 at = mk(1.0f, 1.0f, 1.0f);
+                        if (hit) {
+                            const f3 p = point_on_ray(pr.o, pr.d, bt);
+                            Hit h;
+                            const __amdgpu_buffer_rsrc_t rsa =
+                                __builtin_amdgcn_make_buffer_rsrc((void*)P.code_aux, (short)0, (int)P.code_aux_bytes, 0x00020000);
+                            const int aoff = sphere_record_rs(rsa, p, pr.d, bc, bt, h);
+                            scatter_dc<MODE, true>(ps, pr, h, [&]() {
+                                const u32x4 m = __builtin_amdgcn_raw_buffer_load_b128(rsa, aoff, 32, 0);
+                                return DielRegs{__uint_as_float(m.y), __uint_as_float(m.z), __uint_as_float(m.w)};
+                            });
+                            // (the attenuation only where the path ends here, a bounce cap of 1: a survivor's is restored
+                            // when its entry is dealt, so the albedo is not held through the scatter)
+                            if (P.bounces == 1u) {
+                                typedef float f4v __attribute__((ext_vector_type(4)));
+                                const f4v al = __builtin_amdgcn_raw_buffer_load_b128(rsa, aoff, 16, 0);
+                                at = at * mk(al.x * 0.7f, al.y * 0.7f, al.z * 0.7f);
+                            }
+                        }
+                        const bool surv = hit && P.bounces > 1u;
+                        if (live && !surv) {  // a miss, or a hit at a bounce cap of 1: the sample's colour
+                            const float u = 1.0f - st;
+                            const f3 sky = mk(0.54f * u + 0.54f * st, 0.86f * u + 0.7f * st, 0.92f * u + 0.98f * st);
+                            const f3 c = at * sky;
+                            const uint32_t sp = (job_f0 + blk_f) * TK->sample_npix + job_tile * 64u + lane;
+                            float* const o = TK->samples + (unsigned long long)sp * 3u;
+#if defined(HRT_STAMPS) && defined(HRT_DIAG_NOSTORE)
+                            if (c.x == -12345.0f)
+#endif
+                            {
+                                o[0] = c.x;
+                                o[1] = c.y;
+                                o[2] = c.z;
+                            }
+                            if (uint32_t* const tc = TK->tile_cost)
+                                __hip_atomic_fetch_add(tc + job_tile * 64u + lane, hit ? 2u : 1u, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        const unsigned long long sm = __ballot(surv);
+                        blk_cnt = (uint32_t)__popcll(sm);
+                        {
+                            const float4 k0 = blk[2 * threadIdx.x], k1 = blk[2 * threadIdx.x + 1];
+                            ray.o = mk(k0.x, k0.y, k0.z);
+                            ray.d = mk(k0.w, k1.x, k1.y);
+                            s = __float_as_uint(k1.z);
+                            pix = __float_as_uint(k1.w);
+                            sky_t = blk_sky[threadIdx.x];
+                        }
+                        if (surv) {
+                            const uint32_t e = (threadIdx.x & ~63u) + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32),
+                                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+                            uint32_t pl = lane;
+                            asm volatile("" : "+v"(pl));  // the entry word formed here, no part of it held from kernel entry
+                            blk[2 * e] = float4{pr.o.x, pr.o.y, pr.o.z, pr.d.x};
+                            blk[2 * e + 1] = float4{pr.d.y, pr.d.z, __uint_as_float(ps),
+                                                    __uint_as_float(1u | (pl << 1) | ((uint32_t)bc << 7) | EW_RES)};
+                            blk_sky[e] = st;
+                        }
+                    }
+                }
+                if (!resolved) {
+                    blk[2 * threadIdx.x] = float4{pr.o.x, pr.o.y, pr.o.z, pr.d.x};
+                    blk[2 * threadIdx.x + 1] = float4{pr.d.y, pr.d.z, __uint_as_float(ps), __uint_as_float(ew)};
+                }
                 if constexpr (PACKET) {
                     // (bounce cap 0: no query; rays bvh_begin leaves to the full scan: resolved later, qs 0)
                     if (P.bounces > 0u) {  // (wave-uniform: every lane enters the packet walk)
@@ -3497,10 +3640,10 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
-            const uint32_t avail = 64u - blk_next;
+            const uint32_t avail = blk_n() - blk_next;
             // (PACKET: the rank by mbcnt, no 64-bit lane mask held in VGPRs — the packet kernel's register budget; the
             // other instantiations keep the mask: same-box A/B, the mbcnt form cost C3 0.3 %)
-            const uint32_t rank = PACKET ? __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))
+            const uint32_t rank = WAVEQ ? __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))
                                          : (uint32_t)__popcll(m & below);
             const int src = (int)((blk_next + rank) & 63u);
             const float4 b0 = blk[2 * ((threadIdx.x & ~63u) + (uint32_t)src)];
@@ -3518,7 +3661,9 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                     if constexpr (SEAMS) {
                         // one index per sample: frame of the launch x the frame's tile-padded pixels + the pixel, < 2^32
                         // (renderer.cpp sizes the launch), in place of the pair the store multiplied out per sample
-                        pix = (job_f0 + blk_f) * kargs()->sample_npix + job_tile * 64u + (uint32_t)src;
+                        // (an entry resolved at block time names its pixel: the entries are compacted)
+                        pix = (job_f0 + blk_f) * kargs()->sample_npix + job_tile * 64u +
+                              (BLOCKRES && (ok & EW_RES) ? (ok >> 1) & 63u : (uint32_t)src);
                     } else {
                         fl = sample_ref<FM>(J, job_f0, blk_f);
                         pix = job_tile * 64u + (uint32_t)src;
@@ -3526,6 +3671,16 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                     sky_t = ray.d.y * 0.5f + 0.5f;
                     att = mk(1.0f, 1.0f, 1.0f);
                     bounce = 0;
+                    if constexpr (BLOCKRES) {
+                        // resolved and scattered at block time: the path's sky_t, and the attenuation of its first hit
+                        // from the winner's record, by its code
+                        if (ok & EW_RES) {
+                            const SphereAux* const w = P.code_aux + ((ok & ~EW_RES) >> 7);
+                            sky_t = blk_sky[(threadIdx.x & ~63u) + (uint32_t)src];
+                            att = att * mk(w->ar * 0.7f, w->ag * 0.7f, w->ab * 0.7f);
+                            bounce = 1;
+                        }
+                    }
                     if constexpr (!SEAMS) have = true;
                     qs = 0;
                     if constexpr (PACKET) {
@@ -3539,7 +3694,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             }
             job_dealt<FM>(J, (uint32_t)__popcll(__ballot(took)));
             blk_next += min((uint32_t)__popcll(m), avail);
-            if (blk_next == 64u && blk_f + 1u >= job_nf) job_close(J, lane);
+            if (blk_next == blk_n() && blk_f + 1u >= job_nf) job_close(J, lane);
             m = __ballot(SEAMS ? qs == QS_IDLE : need);
         }
 #ifdef HRT_STAMPS
@@ -3557,7 +3712,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         HRT_LANES(0, (SEAMS ? has() : have) && qs == 0u);
         if (SEAMS ? qs == 0u : have && qs == 0u) {
             if (bounce < P.bounces) {
-                qs = bvh_begin<true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : 2u;
+                qs = bvh_begin<true, true, true, COUNT, LLDS>(P, ray, FLT_MAX_REF, Q, tally, lgeo) ? 1u : BLOCKRES ? QS_FULL : 2u;
             } else {  // bounce cap 0: the sample is the sky colour
                 qs = 3u;
             }
@@ -3580,13 +3735,18 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         // (PACKET: the queries shaded this round counted per wave — a wave-uniform count needs no VGPR; the others count
         // per lane, as before)
         if constexpr (PACKET) queries += (uint32_t)__popcll(__ballot(have && (qs == 2u || qs == 4u)));
+        if constexpr (BLOCKRES) {
+            const uint32_t nf = (uint32_t)__popcll(__ballot(qs == QS_FULL));
+            queries += (uint32_t)__popcll(__ballot(qs == 2u)) + nf;
+            nfull += nf;
+        }
         if (SEAMS ? (int)qs >= 2 : have && qs >= 2u) {
 #ifdef HRT_STAMPS
             tally.lshade++;
             if (first_active_lane()) tally.wshade++;
 #endif
             bool done = true;
-            if (qs == 2u || (PACKET && qs == 4u)) {
+            if (qs == 2u || (PACKET && qs == 4u) || (BLOCKRES && qs == QS_FULL)) {
                 float best = FLT_MAX_REF;
                 int bi;
                 f3 p;
@@ -3597,8 +3757,12 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                     // the winner's record by its BVH code (code_aux: no slot lookup); the rare full scan yields a slot,
                     // which indexes the slot-order records behind the code-order ones
                     bi = Q.bc;
-                    if (Q.full_scan != 0u) {
-                        bi = bvh_end<true>(P, ray, Q, best, tally);
+                    if (BLOCKRES ? qs == QS_FULL : Q.full_scan != 0u) {
+                        if constexpr (BLOCKRES) {  // (bvh_end's full scan, without reading Q.full_scan)
+                            bi = scan_spheres_p<false>(kargs(), ray, best);  // (its sphere tests: nfull, above)
+                        } else {
+                            bi = bvh_end<true>(P, ray, Q, best, tally);
+                        }
                         bi = bi >= 0 ? bi + (int)(P.bvh_nleaf + kargs()->nlarge) : bi;
                     } else {
                         best = Q.bt;
@@ -3608,7 +3772,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
                     bi = bvh_end<true>(P, ray, Q, best, tally);
                     p = point_on_ray(ray.o, ray.d, best);
                 }
-                if constexpr (!PACKET) queries++;
+                if constexpr (!WAVEQ) queries++;
                 if (bi >= 0) {
                     Hit h;
                     if constexpr (SEAMS) {
@@ -3688,7 +3852,14 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     if (lane == 0)
         for (uint32_t c = 0; c < 4u; c++) atomicAdd(P.counter + 5 + c, (unsigned long long)J.get(WJ_STAT + c));
 #endif
-    unsigned long long sums[5] = {(!PACKET || lane == 0u) ? queries : 0u, tally.boxes, tally.spheres, tally.nodes, tally.tris};
+    if constexpr (BLOCKRES) {  // (both counts are the wave's already: no reduction, no lane index held for one)
+        if (lane == 0) {
+            unsigned long long sums[6] = {queries, 0ull, (unsigned long long)nfull * kargs()->nslots, 0ull, 0ull, nres};
+            flush_counts(sums);
+        }
+        return;
+    }
+    unsigned long long sums[5] = {(!WAVEQ || lane == 0u) ? queries : 0u, tally.boxes, tally.spheres, tally.nodes, tally.tris};
 #pragma unroll
     for (int c = 0; c < 5; c++) {
 #pragma unroll
@@ -4106,6 +4277,24 @@ hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* til
 uint32_t hrt_order_scratch_words(uint32_t ntiles) {
     const uint32_t nblocks = (ntiles + ORDER_BLOCK - 1u) / ORDER_BLOCK;
     return OS_BLK + nblocks + nblocks * ORDER_BUCKETS;
+}
+
+// The tiles' primary candidate lists (rt_tile_lists.hpp: the rule, shared with the host mirror): one thread per tile over
+// the leaf spheres, TILE_LIST_WORDS words per tile.
+static_assert(hrt_tiles::K_MAX == TILE_LIST_K && hrt_tiles::WORDS == TILE_LIST_WORDS && hrt_tiles::WALK == TILE_LIST_WALK,
+              "rt_tile_lists.hpp's layout is the kernels'");
+__global__ __launch_bounds__(64) void k_tile_lists(const hrt_tiles::View V, const float4* __restrict__ bvh_sph, uint32_t nleaf,
+                                                   uint32_t* __restrict__ lists) {
+    const uint32_t tile = blockIdx.x * 64u + threadIdx.x;
+    if (tile >= V.tiles_w * V.tiles_h) return;
+    hrt_tiles::tile_list(V, tile, (const float*)bvh_sph, nleaf, lists + (size_t)tile * hrt_tiles::WORDS);
+}
+hipError_t hrt_launch_tile_lists(const hrt_tiles::View& V, const float4* bvh_sph, uint32_t nleaf, uint32_t* lists,
+                                 hipStream_t stream) {
+    const uint32_t ntiles = V.tiles_w * V.tiles_h;
+    if (ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tile_lists, dim3((ntiles + 63u) / 64u), dim3(64), 0, stream, V, bvh_sph, nleaf, lists);
+    return hipGetLastError();
 }
 
 // Exactness check of the range-restricted sqrt / division sequences (rt_device.hpp) against the IEEE

@@ -51,6 +51,26 @@ def regroup_keys(origins, dirs, lo, hi):
     return out
 
 
+def host_tile_lists(camera, width: int, height: int, spheres, *, row0: int = 0, row_step: int = 1, row_block: int = 1,
+                    min_sphere_slots: int = 0, k: int = 8):
+    """Test-only (include/hrt_testing.h rt_host_tile_lists, host only): the per-tile primary candidate lists the renderer
+    builds on the device, uint32[tiles, 9]: the count (0xFFFFFFFF: the tile walks), then the BVH codes."""
+    import ctypes as C
+
+    import numpy as np
+
+    cam = np.ascontiguousarray(camera).tobytes()
+    sp = np.ascontiguousarray(spheres).tobytes()
+    n = C.c_size_t(0)
+    args = (cam, width, height, row0, row_step, row_block, sp, len(spheres), min_sphere_slots, k)
+    _lib.check(lib().rt_host_tile_lists(*args, None, 0, C.byref(n)), "rt_host_tile_lists")
+    words = np.zeros(n.value, dtype=np.uint32)
+    if n.value:
+        _lib.check(lib().rt_host_tile_lists(*args, words.ctypes.data_as(_lib._PU32), n.value, C.byref(n)),
+                   "rt_host_tile_lists")
+    return words.reshape(-1, 9)
+
+
 def sphere_bvh_leaves(spheres, min_sphere_slots: int = 0) -> dict:
     """Test-only (include/hrt_testing.h rt_testing_sphere_bvh_leaves, host only): the culling BVH the renderer builds over
     `spheres` padded with zero slots to min_sphere_slots, as {"leaves": [(first, count), ...] in BVH order, "slots": the
@@ -75,6 +95,7 @@ def sphere_bvh_leaves(spheres, min_sphere_slots: int = 0) -> dict:
 
 
 __all__ = [
+    "host_tile_lists",
     "HIT_DTYPE", "RT_HIT_FRONT", "RT_HIT_TRIANGLE", "RT_T_MISS",
     "LIB_PATH", "RT_FOLD_AUTO", "RT_FOLD_BUFFER", "RT_FOLD_NEXT", "RT_FOLD_RING", "RT_MODE_MIXED", "RT_SCHEDULE_AUTO", "RT_SCHEDULE_QUEUE", "RT_SCHEDULE_TILES", "RT_MODE_SPHERE", "RT_MODE_TRIS", "RtError", "RtParams", "RtStats", "lib",
     "CAMERA_DTYPE", "DIELECTRIC", "LAMBERTIAN", "MATERIAL_DTYPE", "MAX_OBJECT_IN_SCENE", "METAL", "NODE_DTYPE",

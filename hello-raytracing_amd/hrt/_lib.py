@@ -211,6 +211,11 @@ TESTING_SIGNATURES = {
     "rt_testing_set_descent_hold": (C.c_int, [_P, _U32]),
     "rt_testing_get_tile_order": (C.c_int, [_P, _PU32, _PU32, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_testing_set_trace_rays_per_lane": (C.c_int, [_P, _U32]),
+    "rt_testing_set_tile_lists": (C.c_int, [_P, _U32, _U32]),
+    "rt_testing_get_tile_lists_resolved": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "rt_testing_get_tile_lists": (C.c_int, [_P, _PU32, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rt_host_tile_lists": (C.c_int, [_P, _U32, _U32, _U32, _U32, _U32, _P, _U32, _U32, _U32, _PU32, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
     "rt_testing_sphere_bvh_leaves": (C.c_int, [C.POINTER(C.c_float), _U32, C.POINTER(_U32), _U32,
                                                C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
     "rt_testing_get_tri_tree": (C.c_int, [_P, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),

@@ -397,6 +397,29 @@ class Renderer:
                                                   n.value, C.byref(n)), "testing_get_tile_order")
         return sums, order
 
+    def set_tile_lists(self, mode: int = 0, k: int = 8) -> None:
+        """Test-only: the per-tile primary candidate lists of k_trace_split, 0 auto, 1 off, 2 on, and the entries a list
+        may hold (include/hrt_testing.h rt_testing_set_tile_lists)."""
+        check(lib().rt_testing_set_tile_lists(self._h, mode, k), "testing_set_tile_lists")
+
+    def tile_lists_resolved(self) -> int:
+        """Test-only: the frame blocks of the last draw whose primary rays were answered when the block was made
+        (include/hrt_testing.h rt_testing_get_tile_lists_resolved)."""
+        n = C.c_uint64(0)
+        check(lib().rt_testing_get_tile_lists_resolved(self._h, C.byref(n)), "testing_get_tile_lists_resolved")
+        return int(n.value)
+
+    def tile_lists(self) -> np.ndarray:
+        """Test-only: the lists for the renderer's camera, spheres, size and row share, uint32[tiles, 9]: the count
+        (0xFFFFFFFF: the tile walks), then the BVH codes (include/hrt_testing.h rt_testing_get_tile_lists)."""
+        n = C.c_size_t(0)
+        check(lib().rt_testing_get_tile_lists(self._h, None, 0, C.byref(n)), "testing_get_tile_lists")
+        words = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(lib().rt_testing_get_tile_lists(self._h, words.ctypes.data_as(_lib._PU32), n.value, C.byref(n)),
+                  "testing_get_tile_lists")
+        return words.reshape(-1, 9)
+
     def set_descent_hold(self, hold: int) -> None:
         """Test-only: the descent hold of k_trace_split (include/hrt_testing.h rt_testing_set_descent_hold)."""
         check(lib().rt_testing_set_descent_hold(self._h, hold), "testing_set_descent_hold")

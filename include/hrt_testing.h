@@ -32,6 +32,33 @@ int rt_testing_set_descent_hold(rt_renderer *r, uint32_t hold);
  *   a new renderer starts with 0. */
 int rt_testing_set_trace_rays_per_lane(rt_renderer *r, uint32_t rays_per_lane);
 
+/* The per-tile primary candidate lists of the sphere program's k_trace_split<true, false, false, false> (a listed tile's
+ *   primary rays are answered and shaded when their frame block is made; same image, same queries).
+ * mode: 0 the renderer's rule (on wherever that kernel draws with a bounce cap of at least 1), 1 off, 2 on (the same rule:
+ *   other kernels never read lists). k: entries a list may hold, 0..8; a tile with more candidates is marked "walk" and
+ *   its blocks walk their primary rays. RT_ERR_ARG outside those ranges. Stays set until changed; a new renderer
+ *   starts with 0 and 8. */
+int rt_testing_set_tile_lists(rt_renderer *r, uint32_t mode, uint32_t k);
+
+/* Blocking read-back of the lists for the renderer's camera, spheres, size, row share and k (built now if the renderer
+ *   does not hold them): 9 words per 8x8 tile, raster order over the renderer's rows: the count, or 0xFFFFFFFF for a
+ *   tile marked "walk", then the BVH codes (positions in BVH order, rt_testing_sphere_bvh_leaves) ascending, then zeros.
+ *   count: the words, always written. With cap 0 only the count is returned; a smaller cap otherwise is RT_ERR_ARG. */
+int rt_testing_get_tile_lists(rt_renderer *r, uint32_t *words_out, size_t cap, size_t *count);
+
+/* The frame blocks of the last draw (all its launches) whose primary rays k_trace_split answered and shaded when it made
+ *   them; 0 for a draw that walked every primary ray (lists off, another kernel, every tile marked "walk"). Waits for
+ *   the draw, as rt_get_stats. */
+int rt_testing_get_tile_lists_resolved(rt_renderer *r, uint64_t *blocks);
+
+/* The same lists on the host, no device: the rule is one inline function host and device both compile (f64, +, -, *, /
+ *   and sqrt alone), so the device lists equal these byte for byte. camera80, spheres48, min_sphere_slots: as
+ *   rt_set_camera, rt_set_spheres and rt_params; row0, row_step, row_block: the row share of rt_params (a whole image: 0,
+ *   1, 1). count and cap as above. RT_ERR_ARG: a null pointer, a zero width, height or row_step, k above 8. */
+int rt_host_tile_lists(const void *camera80, uint32_t width, uint32_t height, uint32_t row0, uint32_t row_step,
+                       uint32_t row_block, const void *spheres48, uint32_t n, uint32_t min_sphere_slots, uint32_t k,
+                       uint32_t *words_out, size_t cap, size_t *count);
+
 /* The leaves of the sphere culling BVH the renderer would build over n_slots slots (centers_radii: cx, cy, cz, radius per
  *   slot, padding slots as zeros). Host only, no device.
  * leaves: one word per leaf in BVH order, first << 4 | count (first: the leaf's first position in BVH order).

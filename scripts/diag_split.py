@@ -20,13 +20,18 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--suspend", type=int, nargs="+", default=[1, 8, 16, 24, 32, 48])
 ap.add_argument("--hold", type=int, nargs="+", default=[None])
 ap.add_argument("--frames", type=int, default=64)
+ap.add_argument("--count-tests", type=int, default=None,
+                help="rt_params.count_tests; 0: the uncounted kernel, which answers listed tiles' primary rays when it makes "
+                     "their frame block (the box and sphere test figures are then 0; rounds and shade lanes hold)")
+ap.add_argument("--steal", type=int, default=None,
+                help="rt_params.steal (1: off — a launch that steals runs the stealing kernel, which walks its primary rays)")
 ap.add_argument("--leaf", action="store_true",
                 help="the library was built with -DHRT_LEAFSTAT too: the leaf step's first-pass and root-pass counts")
 a = ap.parse_args()
 sd = scenes.config_c3(1920, 1080, a.frames)
 for sb, hold in ((sb, hold) for sb in a.suspend for hold in a.hold):
     r = scenes.make_renderer(sd)
-    r.set_params(variant=4, schedule=2, suspend_below=sb)
+    r.set_params(variant=4, schedule=2, suspend_below=sb, **({} if a.count_tests is None else {"count_tests": a.count_tests}), **({} if a.steal is None else {"steal": a.steal}))
     if hold is not None:
         r.set_descent_hold(hold)
     r.draw_frames(sd.frames, 1000, 10)

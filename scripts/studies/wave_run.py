@@ -2,9 +2,12 @@
 
 usage: python scripts/studies/wave_run.py [--config c3] [--waves 40] [--jobs 6] [--suspend 24] [--hold 0 8 12 ...]
        python scripts/studies/wave_run.py --hold 12 --cand-hold 0/0 8/1 12/1 16/2 24/4 64/2   
+       python scripts/studies/wave_run.py --hold 12 --block-time 0 1            
        python scripts/studies/wave_run.py --calibrate      (suspend_below 24, hold 0 against the GPU's diagnostic counters)
 Builds the simulator with g++ into a temporary directory, writes the scene beside it and prints the simulator's counts
 per setting; with several settings, a table of the wave's box steps, lanes per box step and the modelled issue cost.
+--block-time 1 answers and shades a listed tile's primary rays when their block is made; the lists' lengths are
+rt_host_tile_lists's (the built library's host mirror, no GPU).
 --calibrate compares six figures with scripts/diag_split.py's committed counters (profiles/r05/diag_c/diag_split_c3.log,
 the suspend_below 24 line) and fails when one is off by more than 5 %.
 """
@@ -35,10 +38,12 @@ ap.add_argument("--hold", type=int, nargs="+", default=[0])
 ap.add_argument("--cand-hold", nargs="+", default=["0/0"], metavar="CHOLD/CWAIT",
                 help="the candidate hold priced in round 10 (0/0 = none): the root pass waits for CHOLD lanes with a "
                      "candidate, at most CWAIT iterations")
+ap.add_argument("--block-time", type=int, nargs="+", default=[0], choices=[0, 1],
+                help="1: primary rays of listed tiles answered and shaded when their block is made (round 13)")
 ap.add_argument("--calibrate", action="store_true")
 a = ap.parse_args()
 if a.calibrate:
-    a.suspend, a.hold, a.cand_hold = [24], [0], ["0/0"]
+    a.suspend, a.hold, a.cand_hold, a.block_time = [24], [0], ["0/0"], [0]
 
 sd = scenes.CONFIGS[a.config]()
 assert sd.bvh is None, "the model is of the sphere program"
@@ -52,23 +57,34 @@ with tempfile.TemporaryDirectory() as tmp:
                     str(ROOT / "scripts" / "studies" / "wave_sim.cpp"),
                     str(ROOT / "hello-raytracing_amd" / "csrc" / "host" / "sphere_bvh.cpp")], check=True)
     scene.write_bytes(cam + struct.pack("<I", len(sph) // 48) + sph)
+    lens = Path(tmp) / "tile_list_lengths.bin"
+    if 1 in a.block_time:
+        import hrt  # noqa: E402
+
+        lists = hrt.host_tile_lists(sd.camera, sd.width, sd.height, sd.spheres)
+        lens.write_bytes(np.ascontiguousarray(lists[:, 0], dtype=np.uint32).tobytes())
+        listed = lists[lists[:, 0] != 0xFFFFFFFF, 0]
+        print(f"tile lists (rt_host_tile_lists): {len(lists)} tiles, {len(lists) - len(listed)} walk, mean length "
+              f"{listed.mean():.3f}, max {listed.max()}\n")
     for sb in a.suspend:
         for hold in a.hold:
             for ch in a.cand_hold:
-                chold, cwait = ch.split("/")
-                out = subprocess.run([str(exe), str(scene), str(sd.width), str(sd.height), str(sd.bounces or 50),
-                                      str(a.waves), str(a.jobs), str(sb), str(hold), str(a.job_frames), chold, cwait],
-                                     capture_output=True, text=True, check=True).stdout
-                print(out.split("\nJSON ", 1)[0] + "\n")
-                rows.append(json.loads(out.split("\nJSON ", 1)[1]))
+                for bt in a.block_time:
+                    chold, cwait = ch.split("/")
+                    out = subprocess.run([str(exe), str(scene), str(sd.width), str(sd.height), str(sd.bounces or 50),
+                                          str(a.waves), str(a.jobs), str(sb), str(hold), str(a.job_frames), chold, cwait,
+                                          str(bt), str(lens)], capture_output=True, text=True, check=True).stdout
+                    print(out.split("\nJSON ", 1)[0] + "\n")
+                    rows.append(json.loads(out.split("\nJSON ", 1)[1]))
 
 if len(rows) > 1:
     base = rows[0]
-    print("suspend_below hold chold/cwait  wave box steps / 64 q  lanes / box step  root runs / 64 q  lanes / run  "
+    print("suspend_below hold chold/cwait block  rounds / 64 q  wave box steps / 64 q  lanes / box step  root runs / 64 q  lanes / run  "
           "issue cost / query  vs the first row")
     for r in rows:
         ch = f"{r['chold']}/{r['cwait']}"
-        print(f"{r['suspend_below']:13d} {r['hold']:4d} {ch:>11s} {r['wave_box_per_64q']:22.2f} {r['box_lanes']:17.1f} "
+        print(f"{r['suspend_below']:13d} {r['hold']:4d} {ch:>11s} {r['blocktime']:5d} {r['rounds_per_64q']:14.3f} "
+              f"{r['wave_box_per_64q']:22.2f} {r['box_lanes']:17.1f} "
               f"{r['root_runs_per_64q']:16.2f} {r['root_lanes']:11.1f} "
               f"{r['cost_per_query']:19.3f} {100.0 * (r['cost_per_query'] / base['cost_per_query'] - 1.0):+15.1f} %")
 

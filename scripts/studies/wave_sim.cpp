@@ -16,6 +16,11 @@
 //           its leaf word and its candidates and skips the pop; the wave runs the root pass only once at least `chold`
 //           lanes of the call hold a candidate, or every lane of the call does, or a lane has waited `cwait` iterations.
 //   shade   lanes whose walk has finished: the hit (the oracle's closest_sphere), then scatter or the sample's end.
+//   `blocktime` 1 (round 13, BLOCKRES): a block made for a tile with a primary candidate list is answered and shaded by all
+//           64 lanes when it is made: a miss ends its sample, a hit scatters, and the block's entries are the survivors,
+//           compacted, dealt at bounce 1. The lists' lengths come from rt_host_tile_lists (wave_run.py writes them: one
+//           word per tile, 0xFFFFFFFF for a tile that walks); such a block is charged a begin, a shade at 64 lanes, 60
+//           for compaction and entry writes, 67 for the root passes and 20 per listed sphere on top of the block's own.
 // Paths are the oracle's (make_ray / closest_sphere / scatter, oracle/rt_oracle.c); the tree is build_sphere_bvh's with
 // its f32 boxes unpadded, as in packet_sim.cpp — a model of the kernel's padded fp16 test, not the test itself.
 //
@@ -71,11 +76,14 @@ struct Counts {  // w*: wave events, l*: lanes taking part
     double wbox = 0, lbox = 0, wleaf = 0, lleaf = 0, leaf_maxcnt = 0, leaf_maxcand = 0, whold = 0, lheld = 0;
     double wroot = 0, lroot = 0, wchold = 0, lcheld = 0;  // root-pass runs and their lanes (leaf_maxcand: their iterations)
     double wshade = 0, lshade = 0;
+    double wres = 0, lres = 0, res_list = 0, res_surv = 0;  // blocks resolved when made: their rays, listed spheres, survivors
 };
 
 struct Sim {
     o_scene sc;
     uint32_t W, H, B, suspend_below, hold, job_frames, chold = 0, cwait = 0;
+    bool blocktime = false;
+    std::vector<uint32_t> list_len;  // per tile, 0xFFFFFFFF: walk
     Counts C;
 
     ray_t primary(uint32_t x, uint32_t y, uint32_t time, uint32_t& s) {  // fs_main prologue (oracle sample_pixel)
@@ -230,16 +238,16 @@ struct Sim {
     void wave(uint32_t njobs, uint32_t& seed) {
         Lane lanes[64];
         const uint32_t tw = (W + 7) / 8, th = (H + 7) / 8;
-        uint32_t job = 0, job_tile = 0, job_f0 = 0, blk_f = 0, blk_next = 64;
+        uint32_t job = 0, job_tile = 0, job_f0 = 0, blk_f = 0, blk_next = 64, blk_cnt = 64;
         bool dealing = false, drained = false;
-        struct Entry { ray_t r; uint32_t s; bool ok; } blk[64];
+        struct Entry { ray_t r; uint32_t s; bool ok; uint32_t bounce; } blk[64];
         while (true) {
             // refill
             std::vector<int> need;
             for (int l = 0; l < 64; l++)
                 if (!lanes[l].have && !drained) need.push_back(l);
             while (!need.empty()) {
-                if (blk_next == 64) {
+                if (blk_next == blk_cnt) {
                     if (dealing && blk_f + 1 < job_frames) {
                         blk_f++;
                     } else {
@@ -260,10 +268,31 @@ struct Sim {
                     for (int l = 0; l < 64; l++) {
                         const uint32_t x = (job_tile % tw) * 8 + (l & 7), y = (job_tile / tw) * 8 + (l >> 3);
                         blk[l].ok = x < W && y < H;
+                        blk[l].bounce = 0;
                         if (blk[l].ok) blk[l].r = primary(x, y, 1000u + 10u * (job_f0 + blk_f), blk[l].s);
                     }
+                    blk_cnt = 64;
+                    if (blocktime && B >= 1 && list_len[job_tile] != 0xFFFFFFFFu) {
+                        uint32_t n = 0, live = 0;
+                        for (int l = 0; l < 64; l++) {
+                            if (!blk[l].ok) continue;
+                            live++, C.queries++;
+                            hit_t h = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, FLT_MAX_REF, 0, 0};
+                            closest_sphere(&sc, blk[l].r, &h);
+                            if (fabsf(h.t - FLT_MAX_REF) < sc.eps || B == 1) {
+                                C.samples++;
+                                continue;
+                            }
+                            Entry e = blk[l];
+                            e.r = scatter(&sc, &e.s, e.r, &h);
+                            e.bounce = 1;
+                            blk[n++] = e;  // (n <= l: compaction in place)
+                        }
+                        blk_cnt = n;
+                        C.wres++, C.lres += live, C.res_list += list_len[job_tile], C.res_surv += n;
+                    }
                 }
-                const uint32_t avail = 64 - blk_next;
+                const uint32_t avail = blk_cnt - blk_next;
                 C.wdeal++;
                 std::vector<int> still;
                 for (size_t rank = 0; rank < need.size(); rank++) {
@@ -274,7 +303,7 @@ struct Sim {
                     }
                     const Entry& e = blk[blk_next + rank];
                     if (!e.ok) continue;
-                    L.ray = e.r, L.s = e.s, L.bounce = 0, L.have = true, L.qs = 0;
+                    L.ray = e.r, L.s = e.s, L.bounce = e.bounce, L.have = true, L.qs = 0;
                     C.ldeal++;
                 }
                 blk_next += std::min<uint32_t>((uint32_t)need.size(), avail);
@@ -318,7 +347,7 @@ struct Sim {
 int main(int argc, char** argv) {
     if (argc < 9) {
         fprintf(stderr, "usage: wave_sim scene.bin W H bounces waves jobs_per_wave suspend_below hold [job_frames = 32] "
-                        "[chold = 0] [cwait = 0]\n");
+                        "[chold = 0] [cwait = 0] [blocktime = 0] [tile_list_lengths.bin]\n");
         return 2;
     }
     FILE* f = fopen(argv[1], "rb");
@@ -335,6 +364,14 @@ int main(int argc, char** argv) {
     S.suspend_below = std::max(atoi(argv[7]), 1), S.hold = atoi(argv[8]);
     S.job_frames = argc > 9 ? atoi(argv[9]) : 32;
     S.chold = argc > 10 ? atoi(argv[10]) : 0, S.cwait = argc > 11 ? atoi(argv[11]) : 0;
+    S.blocktime = argc > 12 && atoi(argv[12]) != 0;
+    if (S.blocktime) {
+        const size_t nt = (size_t)((S.W + 7) / 8) * ((S.H + 7) / 8);
+        S.list_len.resize(nt);
+        FILE* lf = argc > 13 ? fopen(argv[13], "rb") : nullptr;
+        if (!lf || fread(S.list_len.data(), 4, nt, lf) != nt) return 3;
+        fclose(lf);
+    }
     std::vector<float> cr(4 * nsl);
     for (uint32_t i = 0; i < nsl; i++) {
         cr[4 * i] = sph[i].center[0], cr[4 * i + 1] = sph[i].center[1], cr[4 * i + 2] = sph[i].center[2];
@@ -375,17 +412,25 @@ int main(int argc, char** argv) {
            C.wroot / q64, C.leaf_maxcand / q64, C.lroot / std::max(C.wroot, 1.0), S.chold, S.cwait, C.wchold / q64,
            C.lcheld / std::max(C.wchold, 1.0));
     // issue-slot price per query (rough weights, see the head of this file)
-    const double c_refill = 340.0 * C.wblock + 40.0 * C.wdeal, c_begin = 130.0 * C.wbegin, c_shade = 260.0 * C.wshade;
+    // (a block resolved when made: its begin, shade, compaction, root passes and listed spheres, charged to the refill)
+    const double c_res = (130.0 + 260.0 + 60.0 + 67.0) * C.wres + 20.0 * C.res_list;
+    if (S.blocktime)
+        printf("block time: %.0f of %.0f blocks resolved (%.1f rays, %.2f listed spheres, %.1f survivors each), %.3f of the "
+               "queries\n",
+               C.wres, C.wblock, C.lres / std::max(C.wres, 1.0), C.res_list / std::max(C.wres, 1.0),
+               C.res_surv / std::max(C.wres, 1.0), C.lres / q);
+    const double c_refill = 340.0 * C.wblock + 40.0 * C.wdeal + c_res, c_begin = 130.0 * C.wbegin, c_shade = 260.0 * C.wshade;
     const double c_walk = 51.0 * C.wbox + 50.0 * C.wcall + 15.0 * C.leaf_maxcnt + 45.0 * C.leaf_maxcand + 12.0 * C.wwalk;
     const double tot = c_refill + c_begin + c_walk + c_shade;
-    printf("issue cost per query %.3f  shares: refill %.3f begin %.3f walk %.3f shade %.3f\n", tot / q, c_refill / tot,
-           c_begin / tot, c_walk / tot, c_shade / tot);
+    printf("issue cost per query %.3f  shares: refill %.3f (block time %.3f of the total) begin %.3f walk %.3f shade %.3f\n",
+           tot / q, c_refill / tot, c_res / tot, c_begin / tot, c_walk / tot, c_shade / tot);
     printf("JSON {\"suspend_below\": %u, \"hold\": %u, \"queries\": %.0f, \"walk_lanes\": %.3f, \"box_lanes\": %.3f, "
            "\"leaf_lanes\": %.3f, \"shade_lanes\": %.3f, \"wave_box_per_64q\": %.4f, \"lane_box_per_q\": %.4f, \"cost_per_query\": %.4f, "
            "\"share_refill\": %.4f, \"share_begin\": %.4f, \"share_walk\": %.4f, \"share_shade\": %.4f, \"chold\": %u, "
-           "\"cwait\": %u, \"root_runs_per_64q\": %.4f, \"root_iterations_per_64q\": %.4f, \"root_lanes\": %.3f}\n",
+           "\"cwait\": %u, \"root_runs_per_64q\": %.4f, \"root_iterations_per_64q\": %.4f, \"root_lanes\": %.3f, \"blocktime\": %d, \"rounds_per_64q\": %.4f, "
+           "\"share_blocktime\": %.4f}\n",
            S.suspend_below, S.hold, q, C.lwalk / C.wwalk, C.lbox / C.wbox, C.lleaf / C.wleaf, C.lshade / C.wshade, C.wbox / q64,
            C.lbox / q, tot / q, c_refill / tot, c_begin / tot, c_walk / tot, c_shade / tot, S.chold, S.cwait, C.wroot / q64,
-           C.leaf_maxcand / q64, C.lroot / std::max(C.wroot, 1.0));
+           C.leaf_maxcand / q64, C.lroot / std::max(C.wroot, 1.0), (int)S.blocktime, r / q64, c_res / tot);
     return 0;
 }

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -1171,6 +1172,25 @@ void delete_buffers(rt_renderer* r) {
     r->cost_tiles = r->order_tiles = 0;
 }
 
+// True when one of `ptrs` is not a multiple of `align` bytes. Null passes: an optional buffer that was not given.
+bool misaligned(size_t align, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p % align) return true;
+    return false;
+}
+
+// What every ray query sets up once its arguments are checked, in this order: the renderer's device made current, the
+// scene's kernel arguments (scene_params) and the scan variant a tiles draw would run. rc: the first failure.
+struct QueryScope {
+    DeviceScope ds;
+    hrt_dev::KParams P{};
+    int variant = hrt_dev::SCAN_SIMPLE, rc;
+    explicit QueryScope(rt_renderer* r) : ds(r->device), rc(ds.rc) {
+        if (!rc) rc = scene_params(r, P);
+        if (!rc && r->mode != RT_MODE_TRIS) variant = resolve_variant(r);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1706,16 +1726,12 @@ int rt_cast_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev, 
     if (!r) return fail(RT_ERR_ARG, "rt_cast_rays: null");
     if (n == 0) return RT_OK;
     if (!origins_dev || !dirs_dev || !hits_dev) return fail(RT_ERR_ARG, "rt_cast_rays: null buffer");
-    if ((uintptr_t)hits_dev % 16u || (uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u)
+    if (misaligned(16, {hits_dev}) || misaligned(4, {origins_dev, dirs_dev}))
         return fail(RT_ERR_ARG, "rt_cast_rays: hits must be 16-byte aligned, origins and directions 4-byte aligned");
     static_assert(sizeof(rt_hit) == 32, "rt_hit: two 16-byte stores per record (k_cast_rays)");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
-    HIP_TRY(hrt_launch_cast(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev, n, hits_dev, r->stream));
+    QueryScope q(r);
+    if (q.rc) return q.rc;
+    HIP_TRY(hrt_launch_cast(r->mode, q.variant, q.P, (const float*)origins_dev, (const float*)dirs_dev, n, hits_dev, r->stream));
     return RT_OK;
 }
 
@@ -1724,15 +1740,11 @@ int rt_occluded(rt_renderer* r, const void* origins_dev, const void* dirs_dev, c
     if (!r) return fail(RT_ERR_ARG, "rt_occluded: null");
     if (n == 0) return RT_OK;
     if (!origins_dev || !dirs_dev || !occluded_dev) return fail(RT_ERR_ARG, "rt_occluded: null buffer");
-    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u || (uintptr_t)tmax_dev % 4u)
+    if (misaligned(4, {origins_dev, dirs_dev, tmax_dev}))
         return fail(RT_ERR_ARG, "rt_occluded: origins, directions and tmax must be 4-byte aligned");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
-    HIP_TRY(hrt_launch_occluded(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev,
+    QueryScope q(r);
+    if (q.rc) return q.rc;
+    HIP_TRY(hrt_launch_occluded(r->mode, q.variant, q.P, (const float*)origins_dev, (const float*)dirs_dev,
                                 (const float*)tmax_dev, n, occluded_dev, r->stream));
     return RT_OK;
 }
@@ -1758,17 +1770,12 @@ int rt_trace_rays(rt_renderer* r, const void* origins_dev, const void* dirs_dev,
     if (!r) return fail(RT_ERR_ARG, "rt_trace_rays: null");
     if (n == 0) return RT_OK;
     if (!origins_dev || !dirs_dev || !radiance_dev) return fail(RT_ERR_ARG, "rt_trace_rays: null buffer");
-    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u || (uintptr_t)rng_dev % 4u || (uintptr_t)radiance_dev % 4u ||
-        (uintptr_t)queries_dev % 4u)
+    if (misaligned(4, {origins_dev, dirs_dev, rng_dev, radiance_dev, queries_dev}))
         return fail(RT_ERR_ARG, "rt_trace_rays: origins, directions, states, radiance and queries must be 4-byte aligned");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    P.bounces = r->params.bounces;
-    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
-    HIP_TRY(hrt_launch_trace_rays(r->mode, variant, P, (const float*)origins_dev, (const float*)dirs_dev,
+    QueryScope q(r);
+    if (q.rc) return q.rc;
+    q.P.bounces = r->params.bounces;
+    HIP_TRY(hrt_launch_trace_rays(r->mode, q.variant, q.P, (const float*)origins_dev, (const float*)dirs_dev,
                                   (const uint32_t*)rng_dev, seed, n, trace_rays_per_lane(r, n), (float*)radiance_dev,
                                   (uint32_t*)queries_dev, r->stream));
     return RT_OK;
@@ -1785,18 +1792,13 @@ int rt_bounce_rays(rt_renderer* r, const rt_bounce* io, uint32_t n) {
     if (io->count_out_dev && io->count_out_dev == io->count_in_dev)
         return fail(RT_ERR_ARG, "rt_bounce_rays: count_out must not be count_in");
     if (!io->index_in_dev && n > io->paths) return fail(RT_ERR_ARG, "rt_bounce_rays: n exceeds paths without index_in");
-    if ((uintptr_t)io->hits_dev % 16u) return fail(RT_ERR_ARG, "rt_bounce_rays: hits must be 16-byte aligned");
-    if ((uintptr_t)io->origins_dev % 4u || (uintptr_t)io->dirs_dev % 4u || (uintptr_t)io->rng_dev % 4u ||
-        (uintptr_t)io->throughput_dev % 4u || (uintptr_t)io->queries_dev % 4u || (uintptr_t)io->index_in_dev % 4u ||
-        (uintptr_t)io->count_in_dev % 4u || (uintptr_t)io->index_out_dev % 4u || (uintptr_t)io->count_out_dev % 4u)
+    if (misaligned(16, {io->hits_dev})) return fail(RT_ERR_ARG, "rt_bounce_rays: hits must be 16-byte aligned");
+    if (misaligned(4, {io->origins_dev, io->dirs_dev, io->rng_dev, io->throughput_dev, io->queries_dev, io->index_in_dev,
+                       io->count_in_dev, io->index_out_dev, io->count_out_dev}))
         return fail(RT_ERR_ARG, "rt_bounce_rays: every buffer but hits must be 4-byte aligned");
     static_assert(sizeof(rt_bounce) == 88, "rt_bounce: ten pointers and two words (hrt/_lib.py RtBounce)");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    const int variant = r->mode == RT_MODE_TRIS ? hrt_dev::SCAN_SIMPLE : resolve_variant(r);
+    QueryScope q(r);
+    if (q.rc) return q.rc;
     hrt_dev::BounceIO B{};
     B.origins = (float*)io->origins_dev;
     B.dirs = (float*)io->dirs_dev;
@@ -1810,7 +1812,7 @@ int rt_bounce_rays(rt_renderer* r, const rt_bounce* io, uint32_t n) {
     B.count_out = (uint32_t*)io->count_out_dev;
     B.paths = io->paths;
     if (B.count_out) HIP_TRY(hipMemsetAsync(B.count_out, 0, sizeof(uint32_t), r->stream));
-    HIP_TRY(hrt_launch_bounce(r->mode, variant, P, B, n, r->stream));
+    HIP_TRY(hrt_launch_bounce(r->mode, q.variant, q.P, B, n, r->stream));
     return RT_OK;
 }
 
@@ -1830,9 +1832,8 @@ int rt_regroup_paths(rt_renderer* r, const rt_regroup* io, uint32_t n) {
     if (n > RT_REGROUP_MAX_ENTRIES) return fail(RT_ERR_ARG, "rt_regroup_paths: more than RT_REGROUP_MAX_ENTRIES entries");
     if (!io->index_in_dev && n > io->paths) return fail(RT_ERR_ARG, "rt_regroup_paths: n exceeds paths without index_in");
     const bool cell = io->mode == RT_REGROUP_CELL_OCTANT;  // (a buffer the mode does not read is not looked at)
-    if ((cell && ((uintptr_t)io->origins_dev % 4u || (uintptr_t)io->dirs_dev % 4u)) || (!cell && (uintptr_t)io->keys_dev % 4u) ||
-        (uintptr_t)io->index_in_dev % 4u || (uintptr_t)io->count_in_dev % 4u || (uintptr_t)io->index_out_dev % 4u ||
-        (uintptr_t)io->keys_out_dev % 4u)
+    if ((cell ? misaligned(4, {io->origins_dev, io->dirs_dev}) : misaligned(4, {io->keys_dev})) ||
+        misaligned(4, {io->index_in_dev, io->count_in_dev, io->index_out_dev, io->keys_out_dev}))
         return fail(RT_ERR_ARG, "rt_regroup_paths: every buffer must be 4-byte aligned");
     static_assert(sizeof(rt_regroup) == 96, "rt_regroup: seven pointers, two words, six floats, two words (hrt/_lib.py RtRegroup)");
     hrt_regroup::Launch a{};
@@ -1880,14 +1881,11 @@ int rt_primary_rays(rt_renderer* r, uint32_t time, void* origins_dev, void* dirs
         return fail(RT_ERR_ARG, "rt_primary_rays: n_rays must be local_rows x width");
     if (n_rays == 0) return RT_OK;
     if (!origins_dev || !dirs_dev) return fail(RT_ERR_ARG, "rt_primary_rays: null buffer");
-    if ((uintptr_t)origins_dev % 4u || (uintptr_t)dirs_dev % 4u)
+    if (misaligned(4, {origins_dev, dirs_dev}))
         return fail(RT_ERR_ARG, "rt_primary_rays: origins and directions must be 4-byte aligned");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, (float*)origins_dev, (float*)dirs_dev, nullptr, r->stream));
+    QueryScope q(r);
+    if (q.rc) return q.rc;
+    HIP_TRY(hrt_launch_primary_rays(r->mode, q.P, time, (float*)origins_dev, (float*)dirs_dev, nullptr, r->stream));
     return RT_OK;
 }
 
@@ -1898,13 +1896,10 @@ int rt_primary_rng(rt_renderer* r, uint32_t time, void* rng_dev, size_t n_rays) 
         return fail(RT_ERR_ARG, "rt_primary_rng: n_rays must be local_rows x width");
     if (n_rays == 0) return RT_OK;
     if (!rng_dev) return fail(RT_ERR_ARG, "rt_primary_rng: null buffer");
-    if ((uintptr_t)rng_dev % 4u) return fail(RT_ERR_ARG, "rt_primary_rng: the states must be 4-byte aligned");
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    hrt_dev::KParams P{};
-    int rc = scene_params(r, P);
-    if (rc) return rc;
-    HIP_TRY(hrt_launch_primary_rays(r->mode, P, time, nullptr, nullptr, (uint32_t*)rng_dev, r->stream));
+    if (misaligned(4, {rng_dev})) return fail(RT_ERR_ARG, "rt_primary_rng: the states must be 4-byte aligned");
+    QueryScope q(r);
+    if (q.rc) return q.rc;
+    HIP_TRY(hrt_launch_primary_rays(r->mode, q.P, time, nullptr, nullptr, (uint32_t*)rng_dev, r->stream));
     return RT_OK;
 }
 

@@ -2636,6 +2636,16 @@ __global__ __launch_bounds__(256) void k_render(const KParams P) {
     if (lane == 0) flush_counts(sums);
 }
 
+// Ray i of the caller's packed 3 x f32 origins and directions (12-B stride): the one load of every ray query below.
+__device__ __forceinline__ Ray load_ray(const float* origins, const float* dirs, size_t i) {
+    const float* const po = origins + i * 3u;
+    const float* const pd = dirs + i * 3u;
+    Ray ray;
+    ray.o = mk(po[0], po[1], po[2]);
+    ray.d = mk(pd[0], pd[1], pd[2]);
+    return ray;
+}
+
 // Closest-hit queries for the caller's rays (rt_cast_rays): one ray per lane, the query k_render runs per bounce —
 // closest_hit with the same per-lane lists, FLT_MAX_REF start and tie rules — and one 32-byte record per ray (include/hrt.h
 // rt_hit) as two 16-B stores. Origins and directions are packed 3 x f32 (12-B stride). Reads the scene only: no image,
@@ -2647,11 +2657,7 @@ __global__ __launch_bounds__(256) void k_cast_rays(const KParams P, const float*
     const LaneLists lists = lane_lists<MODE, SCAN>();
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float* const po = origins + (size_t)i * 3u;
-    const float* const pd = dirs + (size_t)i * 3u;
-    Ray ray;
-    ray.o = mk(po[0], po[1], po[2]);
-    ray.d = mk(pd[0], pd[1], pd[2]);
+    const Ray ray = load_ray(origins, dirs, i);
     Tally tally;
     Hit h;
     int tri = -1;
@@ -2677,11 +2683,7 @@ __global__ __launch_bounds__(256) void k_occluded(const KParams P, const float* 
     const LaneLists lists = lane_lists<MODE, SCAN>();
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float* const po = origins + (size_t)i * 3u;
-    const float* const pd = dirs + (size_t)i * 3u;
-    Ray ray;
-    ray.o = mk(po[0], po[1], po[2]);
-    ray.d = mk(pd[0], pd[1], pd[2]);
+    const Ray ray = load_ray(origins, dirs, i);
     const float tm = tmax != nullptr ? tmax[i] : FLT_MAX_REF;
     occluded[i] = any_hit<MODE, SCAN, TSAH>(P, ray, tm, lists.sphere, lists.tri, lists.tri) ? (uint8_t)1 : (uint8_t)0;
 }
@@ -2716,10 +2718,7 @@ __global__ __launch_bounds__(256) void k_radiance_rays(const KParams P, const fl
     float sky_t = 0.0f;
     uint32_t s = 0, bounce = 0, queries = 0;
     if (i < end) {
-        const float* const po = origins + i * 3u;
-        const float* const pd = dirs + i * 3u;
-        ray.o = mk(po[0], po[1], po[2]);
-        ray.d = mk(pd[0], pd[1], pd[2]);
+        ray = load_ray(origins, dirs, i);
         s = rng != nullptr ? rng[i] : ((uint32_t)i + 1u) * seed;
         sky_t = ray.d.y * 0.5f + 0.5f;
     }
@@ -2748,10 +2747,7 @@ __global__ __launch_bounds__(256) void k_radiance_rays(const KParams P, const fl
             if (queries_out != nullptr) queries_out[i] = queries;
             i += 64u;
             if (i < end) {
-                const float* const po = origins + i * 3u;
-                const float* const pd = dirs + i * 3u;
-                ray.o = mk(po[0], po[1], po[2]);
-                ray.d = mk(pd[0], pd[1], pd[2]);
+                ray = load_ray(origins, dirs, i);
                 s = rng != nullptr ? rng[i] : ((uint32_t)i + 1u) * seed;
                 sky_t = ray.d.y * 0.5f + 0.5f;
                 att = mk(1.0f, 1.0f, 1.0f);
@@ -2787,15 +2783,15 @@ __global__ __launch_bounds__(256) void k_bounce_rays(const KParams P, const Boun
     if (active) {
         float* const po = io.origins + (size_t)j * 3u;
         float* const pd = io.dirs + (size_t)j * 3u;
-        Ray ray;
-        ray.o = mk(po[0], po[1], po[2]);
-        ray.d = mk(pd[0], pd[1], pd[2]);
+        Ray ray = load_ray(io.origins, io.dirs, j);
         Tally tally;
         Hit h;
         int tri = -1;
         hit = closest_hit<MODE, SCAN, TSAH>(P, ray, h, lists.sphere, tally, lists.tri, lists.tri, &tri);
         if (io.queries != nullptr) io.queries[j] += 1u;
-        if (io.hits != nullptr) {  // (k_cast_rays' record, of the ray before the scatter)
+        // k_cast_rays' record, of the ray before the scatter: the packing is written out a second time on purpose (a
+        // shared helper changed the register allocation of every instantiation of both kernels).
+        if (io.hits != nullptr) {
             uint4 lo = {__float_as_uint(FLT_MAX_REF), 0xFFFFFFFFu, 0u, 0u}, hi = {0u, 0u, 0u, 0u};  // miss: t, prim -1, zeros
             if (hit) {
                 const bool sphere = MODE == MODE_SPHERE || (MODE == MODE_MIXED && (h.id & 4u) != 0u);
@@ -4726,46 +4722,42 @@ static hipError_t launch_split_tris(const KParams& P, hipStream_t stream) {
     }
 }
 
-// Sample queue, part 1: trace every sample of the chunk into P.samples.
-// variant: SCAN_SIMPLE, SCAN_DEFER or SCAN_BVH (resolved by the host); P.tri_bvh picks the triangle walk.
-// The reference heap walk (triangle / mixed programs) and the sphere program's culling BVH always run in the
-// suspendable-walk kernels (renderer.cpp sets suspend_below >= 1 for them; 1 = a wave never leaves a walk early);
-// k_trace is instantiated only for what has no split kernel: the sphere program's linear scans and the opt-in SAH
-// triangle walk (tri_bvh = 1).
+// The one place (program, sphere scan, SAH triangle walk) becomes the template arguments <MODE, SCAN, TSAH>: every kernel
+// family templated on them (k_render, k_trace and k_trace_split_tris, the ray queries) is launched through it, so a new
+// program or scan variant is added here. f is a generic lambda called once as f(KernelSel<MODE, SCAN, TSAH>{}).
+// variant: SCAN_SIMPLE, SCAN_DEFER or SCAN_BVH (resolved by the host; anything else runs as SCAN_BVH). The sphere
+// program has no triangle walk (TSAH false whatever tri_bvh says) and the triangle program no sphere scan (SCAN_SIMPLE):
+// 3 + 2 + 6 = 11 combinations.
+template <int MODE, int SCAN, bool TSAH>
+struct KernelSel {
+    static constexpr int mode = MODE, scan = SCAN;
+    static constexpr bool tsah = TSAH;
+};
+template <int MODE, bool TSAH, typename F>
+static auto with_scan(int variant, F&& f) {
+    if constexpr (MODE == MODE_TRIS) {
+        return f(KernelSel<MODE, SCAN_SIMPLE, TSAH>{});
+    } else {
+        if (variant == SCAN_SIMPLE) return f(KernelSel<MODE, SCAN_SIMPLE, TSAH>{});
+        if (variant == SCAN_DEFER) return f(KernelSel<MODE, SCAN_DEFER, TSAH>{});
+        return f(KernelSel<MODE, SCAN_BVH, TSAH>{});
+    }
+}
+template <typename F>
+static auto with_scene_kernel(int mode, int variant, bool tri_bvh, F&& f) {
+    switch (mode) {
+    case MODE_SPHERE: return with_scan<MODE_SPHERE, false>(variant, f);
+    case MODE_TRIS: return tri_bvh ? with_scan<MODE_TRIS, true>(variant, f) : with_scan<MODE_TRIS, false>(variant, f);
+    default: return tri_bvh ? with_scan<MODE_MIXED, true>(variant, f) : with_scan<MODE_MIXED, false>(variant, f);
+    }
+}
+
 // k_trace<MODE, SCAN, TSAH> or, with the fold ring, k_ring<MODE, SCAN, TSAH> (displayed as k_trace: rt_stats.fold_ring)
 template <int MODE, int SCAN, bool TSAH>
 static hipError_t launch_k_trace(const KParams& P, hipStream_t stream) {
     const char* name = kname("k_trace", MODE, SCAN, (int)TSAH);
     return P.ring_mode ? launch_persistent(k_ring<MODE, SCAN, TSAH>, P, stream, name)
                        : launch_persistent(k_trace<MODE, SCAN, TSAH>, P, stream, name);
-}
-
-template <int MODE, bool TSAH>
-static hipError_t launch_trace_mode(int variant, const KParams& P, hipStream_t stream) {
-    if constexpr (MODE != MODE_SPHERE && !TSAH) {
-        if (P.suspend_below == 0u) return hipErrorInvalidValue;
-        // The mixed program with the culling BVH runs its sphere walk to completion in the begin phase
-        // (stack in the triangle-batch LDS) and suspends only the heap walk: C5 at 256 spp 6.25 -> 6.55
-        // Grays/s. (Splitting both walks measured 5.93; an earlier heap-only form with the stack in
-        // the LDS block region, 6.05.)
-        if constexpr (MODE == MODE_TRIS) {
-            return launch_split_tris<MODE, SCAN_SIMPLE>(P, stream);
-        } else {
-            if (variant == SCAN_SIMPLE) return launch_split_tris<MODE, SCAN_SIMPLE>(P, stream);
-            if (variant == SCAN_DEFER) return launch_split_tris<MODE, SCAN_DEFER>(P, stream);
-            return launch_split_tris<MODE, SCAN_BVH>(P, stream);
-        }
-    } else if constexpr (MODE == MODE_TRIS) {
-        return launch_k_trace<MODE, SCAN_SIMPLE, TSAH>(P, stream);
-    } else {
-        if (variant == SCAN_SIMPLE) return launch_k_trace<MODE, SCAN_SIMPLE, TSAH>(P, stream);
-        if (variant == SCAN_DEFER) return launch_k_trace<MODE, SCAN_DEFER, TSAH>(P, stream);
-        if constexpr (MODE == MODE_SPHERE) {
-            return hipErrorInvalidValue;  // the culling BVH runs in k_trace_split
-        } else {
-            return launch_k_trace<MODE, SCAN_BVH, TSAH>(P, stream);
-        }
-    }
 }
 
 // k_trace_split<LNODES, STEAL, COUNT, PACKET> by P.bvh_lnodes / P.steal / P.packet (PACKET only with LNODES), or with the
@@ -4789,6 +4781,12 @@ static hipError_t launch_trace_split(const KParams& P, hipStream_t stream) {
                         : launch_persistent(k_trace_split<false, false, COUNT, false>, P, stream, kname_bbbb(base, 0, 0, COUNT, 0));
 }
 
+// Sample queue, part 1: trace every sample of the chunk into P.samples.
+// variant: SCAN_SIMPLE, SCAN_DEFER or SCAN_BVH (resolved by the host); P.tri_bvh picks the triangle walk.
+// The reference heap walk (triangle / mixed programs) and the sphere program's culling BVH always run in the
+// suspendable-walk kernels (renderer.cpp sets suspend_below >= 1 for them; 1 = a wave never leaves a walk early);
+// k_trace is instantiated only for what has no split kernel: the sphere program's linear scans and the opt-in SAH
+// triangle walk (tri_bvh = 1).
 hipError_t hrt_launch_trace(int mode, int variant, const KParams& P, hipStream_t stream) {
     if (P.njobs == 0) return hipSuccess;
     // parts of jobs (tail_from) are decoded by the suspendable-walk kernels with the sample buffer and no stealing only
@@ -4796,192 +4794,81 @@ hipError_t hrt_launch_trace(int mode, int variant, const KParams& P, hipStream_t
     const bool split_kernel = mode == MODE_SPHERE ? (variant == SCAN_BVH && P.suspend_below > 0u) : !P.tri_bvh;
     if (P.tail_from != 0xFFFFFFFFu && !(split_kernel && !P.steal && !P.ring_mode)) return hipErrorInvalidValue;
     if (P.steal && P.ring_mode) return hipErrorInvalidValue;  // stealing: the sample buffer only (no such instantiation)
-    switch (mode) {
-    case MODE_SPHERE:
-        if (variant == SCAN_BVH && P.suspend_below > 0u)
-        {
-            return P.count_tests ? launch_trace_split<true>(P, stream) : launch_trace_split<false>(P, stream);
+    if (mode == MODE_SPHERE && variant == SCAN_BVH && P.suspend_below > 0u)
+        return P.count_tests ? launch_trace_split<true>(P, stream) : launch_trace_split<false>(P, stream);
+    return with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) -> hipError_t {
+        if constexpr (sel.mode != MODE_SPHERE && !sel.tsah) {
+            if (P.suspend_below == 0u) return hipErrorInvalidValue;
+            // The mixed program with the culling BVH runs its sphere walk to completion in the begin phase
+            // (stack in the triangle-batch LDS) and suspends only the heap walk: C5 at 256 spp 6.25 -> 6.55
+            // Grays/s. (Splitting both walks measured 5.93; an earlier heap-only form with the stack in
+            // the LDS block region, 6.05.)
+            return launch_split_tris<sel.mode, sel.scan>(P, stream);
+        } else if constexpr (sel.mode == MODE_SPHERE && sel.scan == SCAN_BVH) {
+            return hipErrorInvalidValue;  // the culling BVH runs in k_trace_split
+        } else {
+            return launch_k_trace<sel.mode, sel.scan, sel.tsah>(P, stream);
         }
-        return launch_trace_mode<MODE_SPHERE, false>(variant, P, stream);
-    case MODE_TRIS:
-        return P.tri_bvh ? launch_trace_mode<MODE_TRIS, true>(variant, P, stream)
-                         : launch_trace_mode<MODE_TRIS, false>(variant, P, stream);
-    default:
-        return P.tri_bvh ? launch_trace_mode<MODE_MIXED, true>(variant, P, stream)
-                         : launch_trace_mode<MODE_MIXED, false>(variant, P, stream);
-    }
+    });
 }
 
 // Host-side launcher of the tiles schedule (called from renderer.cpp; no HIP types in the C-ABI).
-// variant: SCAN_SIMPLE, SCAN_DEFER or SCAN_BVH (resolved by the host).
-template <int MODE, bool TSAH>
-static void launch_render_mode(int variant, const KParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-    (void)kname("k_render", MODE, MODE == MODE_TRIS ? SCAN_SIMPLE : variant, (int)TSAH);
-    if constexpr (MODE == MODE_TRIS) {
-        hipLaunchKernelGGL((k_render<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P);
-    } else {
-        if (variant == SCAN_SIMPLE) hipLaunchKernelGGL((k_render<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P);
-        else if (variant == SCAN_DEFER) hipLaunchKernelGGL((k_render<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((k_render<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P);
-    }
-}
-
 hipError_t hrt_launch_render(int mode, int variant, const KParams& P, hipStream_t stream) {
-    dim3 block(256);
-    dim3 grid((P.W + 15u) / 16u, (P.nrows + 15u) / 16u);
+    const dim3 grid((P.W + 15u) / 16u, (P.nrows + 15u) / 16u);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    switch (mode) {
-    case MODE_SPHERE: launch_render_mode<MODE_SPHERE, false>(variant, P, grid, block, stream); break;
-    case MODE_TRIS:
-        if (P.tri_bvh) launch_render_mode<MODE_TRIS, true>(variant, P, grid, block, stream);
-        else launch_render_mode<MODE_TRIS, false>(variant, P, grid, block, stream);
-        break;
-    default:
-        if (P.tri_bvh) launch_render_mode<MODE_MIXED, true>(variant, P, grid, block, stream);
-        else launch_render_mode<MODE_MIXED, false>(variant, P, grid, block, stream);
-        break;
-    }
+    with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) {
+        (void)kname("k_render", sel.mode, sel.mode == MODE_TRIS ? SCAN_SIMPLE : variant, (int)sel.tsah);
+        hipLaunchKernelGGL((k_render<sel.mode, sel.scan, sel.tsah>), grid, dim3(256), 0, stream, P);
+    });
     return hipGetLastError();
 }
 
-// Host-side launcher of rt_cast_rays: the (MODE, SCAN, TSAH) set of the tiles schedule (launch_render_mode), one ray
-// per lane. (No kname: rt_stats.kernel names the last draw's kernel.)
-template <int MODE, bool TSAH>
-static void launch_cast_mode(int variant, const KParams& P, const float* origins, const float* dirs, uint32_t n, uint4* hits,
-                             dim3 grid, dim3 block, hipStream_t stream) {
-    if constexpr (MODE == MODE_TRIS) {
-        hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
-    } else {
-        if (variant == SCAN_SIMPLE)
-            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
-        else if (variant == SCAN_DEFER)
-            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
-        else
-            hipLaunchKernelGGL((k_cast_rays<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, origins, dirs, n, hits);
-    }
-}
+// The ray queries below: k_render's (MODE, SCAN, TSAH) set, and no kname (rt_stats.kernel names the last draw's kernel).
+// Grid of the ray-per-lane ones: ceil(n / 256) workgroups of 256.
+static dim3 ray_grid(uint32_t n) { return dim3((uint32_t)(((unsigned long long)n + 255u) / 256u)); }
 
 hipError_t hrt_launch_cast(int mode, int variant, const KParams& P, const float* origins, const float* dirs, uint32_t n,
                            void* hits, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    dim3 block(256);
-    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
-    uint4* const h = (uint4*)hits;
-    switch (mode) {
-    case MODE_SPHERE: launch_cast_mode<MODE_SPHERE, false>(variant, P, origins, dirs, n, h, grid, block, stream); break;
-    case MODE_TRIS:
-        if (P.tri_bvh) launch_cast_mode<MODE_TRIS, true>(variant, P, origins, dirs, n, h, grid, block, stream);
-        else launch_cast_mode<MODE_TRIS, false>(variant, P, origins, dirs, n, h, grid, block, stream);
-        break;
-    default:
-        if (P.tri_bvh) launch_cast_mode<MODE_MIXED, true>(variant, P, origins, dirs, n, h, grid, block, stream);
-        else launch_cast_mode<MODE_MIXED, false>(variant, P, origins, dirs, n, h, grid, block, stream);
-        break;
-    }
+    with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) {
+        hipLaunchKernelGGL((k_cast_rays<sel.mode, sel.scan, sel.tsah>), ray_grid(n), dim3(256), 0, stream, P, origins, dirs, n,
+                           (uint4*)hits);
+    });
     return hipGetLastError();
 }
 
-// Host-side launcher of rt_bounce_rays: k_cast_rays' instantiation set and grid (one entry per lane; every step of a
-// loop is launched for the first step's n, the kernel reads *count_in).
-template <int MODE, bool TSAH>
-static void launch_bounce_mode(int variant, const KParams& P, const BounceIO& io, uint32_t n, dim3 grid, dim3 block,
-                               hipStream_t stream) {
-    if constexpr (MODE == MODE_TRIS) {
-        hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, io, n);
-    } else {
-        if (variant == SCAN_SIMPLE)
-            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, io, n);
-        else if (variant == SCAN_DEFER)
-            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, io, n);
-        else
-            hipLaunchKernelGGL((k_bounce_rays<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, io, n);
-    }
-}
-
+// rt_bounce_rays: every step of a loop is launched for the first step's n, the kernel reads *count_in.
 hipError_t hrt_launch_bounce(int mode, int variant, const KParams& P, const BounceIO& io, uint32_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    dim3 block(256);
-    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
-    switch (mode) {
-    case MODE_SPHERE: launch_bounce_mode<MODE_SPHERE, false>(variant, P, io, n, grid, block, stream); break;
-    case MODE_TRIS:
-        if (P.tri_bvh) launch_bounce_mode<MODE_TRIS, true>(variant, P, io, n, grid, block, stream);
-        else launch_bounce_mode<MODE_TRIS, false>(variant, P, io, n, grid, block, stream);
-        break;
-    default:
-        if (P.tri_bvh) launch_bounce_mode<MODE_MIXED, true>(variant, P, io, n, grid, block, stream);
-        else launch_bounce_mode<MODE_MIXED, false>(variant, P, io, n, grid, block, stream);
-        break;
-    }
+    with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) {
+        hipLaunchKernelGGL((k_bounce_rays<sel.mode, sel.scan, sel.tsah>), ray_grid(n), dim3(256), 0, stream, P, io, n);
+    });
     return hipGetLastError();
-}
-
-// Host-side launcher of rt_occluded: k_cast_rays' instantiation set and grid.
-template <int MODE, bool TSAH>
-static void launch_occluded_mode(int variant, const KParams& P, const float* origins, const float* dirs, const float* tmax,
-                                 uint32_t n, uint8_t* occ, dim3 grid, dim3 block, hipStream_t stream) {
-    if constexpr (MODE == MODE_TRIS) {
-        hipLaunchKernelGGL((k_occluded<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
-    } else {
-        if (variant == SCAN_SIMPLE)
-            hipLaunchKernelGGL((k_occluded<MODE, SCAN_SIMPLE, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
-        else if (variant == SCAN_DEFER)
-            hipLaunchKernelGGL((k_occluded<MODE, SCAN_DEFER, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
-        else
-            hipLaunchKernelGGL((k_occluded<MODE, SCAN_BVH, TSAH>), grid, block, 0, stream, P, origins, dirs, tmax, n, occ);
-    }
 }
 
 hipError_t hrt_launch_occluded(int mode, int variant, const KParams& P, const float* origins, const float* dirs,
                                const float* tmax, uint32_t n, void* occluded, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    dim3 block(256);
-    dim3 grid((uint32_t)(((unsigned long long)n + 255u) / 256u));
-    uint8_t* const o = (uint8_t*)occluded;
-    switch (mode) {
-    case MODE_SPHERE: launch_occluded_mode<MODE_SPHERE, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream); break;
-    case MODE_TRIS:
-        if (P.tri_bvh) launch_occluded_mode<MODE_TRIS, true>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
-        else launch_occluded_mode<MODE_TRIS, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
-        break;
-    default:
-        if (P.tri_bvh) launch_occluded_mode<MODE_MIXED, true>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
-        else launch_occluded_mode<MODE_MIXED, false>(variant, P, origins, dirs, tmax, n, o, grid, block, stream);
-        break;
-    }
+    with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) {
+        hipLaunchKernelGGL((k_occluded<sel.mode, sel.scan, sel.tsah>), ray_grid(n), dim3(256), 0, stream, P, origins, dirs, tmax, n,
+                           (uint8_t*)occluded);
+    });
     return hipGetLastError();
 }
 
-// Host-side launcher of rt_trace_rays: k_cast_rays' instantiation set; a wave per 64 R rays (k_radiance_rays).
-using RadianceKernel = void (*)(const KParams, const float*, const float*, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                                float*, uint32_t*);
-template <int MODE, bool TSAH>
-static RadianceKernel radiance_kernel(int variant) {
-    if constexpr (MODE == MODE_TRIS) {
-        return k_radiance_rays<MODE, SCAN_SIMPLE, TSAH>;
-    } else {
-        if (variant == SCAN_SIMPLE) return k_radiance_rays<MODE, SCAN_SIMPLE, TSAH>;
-        if (variant == SCAN_DEFER) return k_radiance_rays<MODE, SCAN_DEFER, TSAH>;
-        return k_radiance_rays<MODE, SCAN_BVH, TSAH>;
-    }
-}
-
-// R: rays per lane (>= 1, chosen by the host: renderer.cpp trace_rays_per_lane).
+// rt_trace_rays: a wave per 64 R rays (k_radiance_rays). R: rays per lane (>= 1, chosen by the host: renderer.cpp
+// trace_rays_per_lane).
 hipError_t hrt_launch_trace_rays(int mode, int variant, const KParams& P, const float* origins, const float* dirs,
                                  const uint32_t* rng, uint32_t seed, uint32_t n, uint32_t R, float* radiance, uint32_t* queries,
                                  hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (R == 0) R = 1;
     const unsigned long long waves = ((unsigned long long)n + 64ull * R - 1u) / (64ull * R);
-    dim3 block(256);
-    dim3 grid((uint32_t)((waves + 3u) / 4u));
-    RadianceKernel k;
-    switch (mode) {
-    case MODE_SPHERE: k = radiance_kernel<MODE_SPHERE, false>(variant); break;
-    case MODE_TRIS: k = P.tri_bvh ? radiance_kernel<MODE_TRIS, true>(variant) : radiance_kernel<MODE_TRIS, false>(variant); break;
-    default: k = P.tri_bvh ? radiance_kernel<MODE_MIXED, true>(variant) : radiance_kernel<MODE_MIXED, false>(variant); break;
-    }
-    hipLaunchKernelGGL(k, grid, block, 0, stream, P, origins, dirs, rng, seed, n, R, radiance, queries);
+    const dim3 grid((uint32_t)((waves + 3u) / 4u));
+    with_scene_kernel(mode, variant, P.tri_bvh != 0, [&](auto sel) {
+        hipLaunchKernelGGL((k_radiance_rays<sel.mode, sel.scan, sel.tsah>), grid, dim3(256), 0, stream, P, origins, dirs, rng, seed,
+                           n, R, radiance, queries);
+    });
     return hipGetLastError();
 }
 

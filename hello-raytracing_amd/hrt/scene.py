@@ -54,6 +54,11 @@ def f32(x) -> np.float32:
     return np.float32(x)
 
 
+def _ptr(t):
+    """A torch tensor's device address for a void* argument or field; None (an optional buffer not given) is null."""
+    return t.data_ptr() if t is not None else None
+
+
 @dataclass(frozen=True)
 class Vec3:
     x: float
@@ -450,18 +455,55 @@ class Renderer:
 
         return torch.device("cuda", self.device()[0])
 
-    def _rays_on_device(self, a, what: str):
-        """(N, 3) float32 rays as a contiguous tensor on the renderer's device (numpy arrays are uploaded)."""
+    def _rays_on_device(self, who: str, a, what: str):
+        """(N, 3) float32 rays as a contiguous tensor on the renderer's device (numpy arrays are uploaded). who: the
+        calling method, for the messages."""
         import torch
 
         dev = self._torch_device()
         if not torch.is_tensor(a):
             a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
         if a.dtype != torch.float32 or a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f"cast_rays: {what} must be (N, 3) float32, got {tuple(a.shape)} {a.dtype}")
+            raise ValueError(f"{who}: {what} must be (N, 3) float32, got {tuple(a.shape)} {a.dtype}")
         if a.device != dev:
-            raise ValueError(f"cast_rays: {what} is on {a.device}, the renderer draws on {dev}")
+            raise ValueError(f"{who}: {what} is on {a.device}, the renderer draws on {dev}")
         return a.contiguous()
+
+    def _ray_pair(self, who: str, origins, dirs):
+        """The rays of one query, checked: (origins, dirs, N), both (N, 3) float32 on the renderer's device."""
+        o, d = self._rays_on_device(who, origins, "origins"), self._rays_on_device(who, dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError(f"{who}: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
+        n = int(o.shape[0])
+        if n >= 1 << 32:
+            raise ValueError(f"{who}: at most 2^32 - 1 rays per call")
+        return o, d, n
+
+    def _rng_states(self, who: str, rng, n: int):
+        """The caller's (n,) int32 / uint32 RNG states as a contiguous int32 tensor on the renderer's device."""
+        import torch
+
+        dev = self._torch_device()
+        s = rng
+        if not torch.is_tensor(s):
+            s = np.asarray(s)
+            if s.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+                raise ValueError(f"{who}: rng must be int32 or uint32, got {s.dtype}")
+            s = torch.from_numpy(np.ascontiguousarray(s).view(np.int32)).to(dev)
+        if s.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(s.shape) != (n,):
+            raise ValueError(f"{who}: rng must be ({n},) int32, got {tuple(s.shape)} {s.dtype}")
+        if s.device != dev:
+            raise ValueError(f"{who}: rng is on {s.device}, the renderer draws on {dev}")
+        return s.contiguous()
+
+    def _query(self, who: str, fn, *args) -> None:
+        """One call of a ray query: torch's current stream on the renderer's device is synchronised before it (the
+        caller's tensors are complete) and the renderer after it (so are the results)."""
+        import torch
+
+        torch.cuda.current_stream(self._torch_device()).synchronize()
+        check(fn(self._h, *args), who)
+        self.synchronize()
 
     def stream(self) -> int:
         """The renderer's HIP stream as an integer handle (rt_get_stream), e.g. for torch.cuda.ExternalStream."""
@@ -477,18 +519,9 @@ class Renderer:
         the call and the renderer after it."""
         import torch
 
-        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError(f"cast_rays: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
-        n = int(o.shape[0])
-        if n >= 1 << 32:
-            raise ValueError("cast_rays: at most 2^32 - 1 rays per call")
-        dev = self._torch_device()
-        hits = torch.empty((n, HIT_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_cast_rays(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), n,
-                                 C.c_void_p(hits.data_ptr())), "cast_rays")
-        self.synchronize()
+        o, d, n = self._ray_pair("cast_rays", origins, dirs)
+        hits = torch.empty((n, HIT_DTYPE.itemsize // 4), dtype=torch.int32, device=self._torch_device())
+        self._query("cast_rays", lib().rt_cast_rays, _ptr(o), _ptr(d), n, _ptr(hits))
         f = hits.view(torch.float32)
         return {"t": f[:, 0].clone(), "prim": hits[:, 1].clone(), "normal": f[:, 2:5].clone(),
                 "flags": hits[:, 5].clone(), "material": hits[:, 6].clone()}
@@ -501,12 +534,7 @@ class Renderer:
         torch's current stream before the call and the renderer after it."""
         import torch
 
-        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError(f"occluded: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
-        n = int(o.shape[0])
-        if n >= 1 << 32:
-            raise ValueError("occluded: at most 2^32 - 1 rays per call")
+        o, d, n = self._ray_pair("occluded", origins, dirs)
         dev = self._torch_device()
         t = None
         if tmax is not None:
@@ -525,11 +553,7 @@ class Renderer:
                     raise ValueError(f"occluded: tmax is on {t.device}, the renderer draws on {dev}")
                 t = t.contiguous()
         out = torch.empty((n,), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_occluded(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                C.c_void_p(t.data_ptr()) if t is not None else None, n, C.c_void_p(out.data_ptr())),
-              "occluded")
-        self.synchronize()
+        self._query("occluded", lib().rt_occluded, _ptr(o), _ptr(d), _ptr(t), n, _ptr(out))
         return out != 0
 
     def primary_rays(self, time: int):
@@ -541,10 +565,7 @@ class Renderer:
         shape = (self.local_rows, self.width, 3)
         o = torch.empty(shape, dtype=torch.float32, device=dev)
         d = torch.empty(shape, dtype=torch.float32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_primary_rays(self._h, int(time) & 0xFFFFFFFF, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                    shape[0] * shape[1]), "primary_rays")
-        self.synchronize()
+        self._query("primary_rays", lib().rt_primary_rays, int(time) & 0xFFFFFFFF, _ptr(o), _ptr(d), shape[0] * shape[1])
         return o, d
 
     def first_hit(self, time: int) -> dict:
@@ -563,34 +584,12 @@ class Renderer:
         it."""
         import torch
 
-        o, d = self._rays_on_device(origins, "origins"), self._rays_on_device(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError(f"trace_rays: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
-        n = int(o.shape[0])
-        if n >= 1 << 32:
-            raise ValueError("trace_rays: at most 2^32 - 1 rays per call")
+        o, d, n = self._ray_pair("trace_rays", origins, dirs)
         dev = self._torch_device()
-        s = None
-        if rng is not None:
-            s = rng
-            if not torch.is_tensor(s):
-                s = np.asarray(s)
-                if s.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
-                    raise ValueError(f"trace_rays: rng must be int32 or uint32, got {s.dtype}")
-                s = torch.from_numpy(np.ascontiguousarray(s).view(np.int32)).to(dev)
-            if s.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(s.shape) != (n,):
-                raise ValueError(f"trace_rays: rng must be ({n},) int32, got {tuple(s.shape)} {s.dtype}")
-            if s.device != dev:
-                raise ValueError(f"trace_rays: rng is on {s.device}, the renderer draws on {dev}")
-            s = s.contiguous()
+        s = self._rng_states("trace_rays", rng, n) if rng is not None else None
         rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
         q = torch.empty((n,), dtype=torch.int32, device=dev) if want_queries else None
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_trace_rays(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                  C.c_void_p(s.data_ptr()) if s is not None else None, int(seed) & 0xFFFFFFFF, n,
-                                  C.c_void_p(rad.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None),
-              "trace_rays")
-        self.synchronize()
+        self._query("trace_rays", lib().rt_trace_rays, _ptr(o), _ptr(d), _ptr(s), int(seed) & 0xFFFFFFFF, n, _ptr(rad), _ptr(q))
         return (rad, q) if want_queries else rad
 
     def primary_rng(self, time: int):
@@ -601,10 +600,7 @@ class Renderer:
         dev = self._torch_device()
         shape = (self.local_rows, self.width)
         s = torch.empty(shape, dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_primary_rng(self._h, int(time) & 0xFFFFFFFF, C.c_void_p(s.data_ptr()), shape[0] * shape[1]),
-              "primary_rng")
-        self.synchronize()
+        self._query("primary_rng", lib().rt_primary_rng, int(time) & 0xFFFFFFFF, _ptr(s), shape[0] * shape[1])
         return s
 
     def trace_frame(self, time: int, want_queries: bool = False):
@@ -678,14 +674,8 @@ class Renderer:
         if io is not None and (io.ndim != 1 or int(io.shape[0]) < n):
             raise ValueError(f"bounce_rays: index_out must have room for {n} int32, got {tuple(io.shape)}")
         co = self._bounce_buffer(count_out, "count_out", (1,), i32, optional=True)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
-        b = _lib.RtBounce(ptr(o), ptr(d), ptr(s), ptr(tp), ptr(q), ptr(h), ptr(ii), ptr(ci), ptr(io), ptr(co), paths, 0)
-        torch.cuda.current_stream(self._torch_device()).synchronize()
-        check(lib().rt_bounce_rays(self._h, C.byref(b), n), "bounce_rays")
-        self.synchronize()
+        b = _lib.RtBounce(_ptr(o), _ptr(d), _ptr(s), _ptr(tp), _ptr(q), _ptr(h), _ptr(ii), _ptr(ci), _ptr(io), _ptr(co), paths, 0)
+        self._query("bounce_rays", lib().rt_bounce_rays, C.byref(b), n)
 
     def regroup_paths(self, index_out, origins=None, dirs=None, keys=None, box=None, index_in=None, count_in=None,
                       keys_out=None, n=None, paths=None) -> None:
@@ -741,16 +731,10 @@ class Renderer:
         ko = self._bounce_buffer(keys_out, "keys_out", None, i32, optional=True, who=who)
         if ko is not None and (ko.ndim != 1 or int(ko.shape[0]) < n):
             raise ValueError(f"regroup_paths: keys_out must have room for {n} int32, got {tuple(ko.shape)}")
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
-        g = _lib.RtRegroup(ptr(o), ptr(d), ptr(kk), ptr(ii), ptr(ci), ptr(io), ptr(ko), paths,
+        g = _lib.RtRegroup(_ptr(o), _ptr(d), _ptr(kk), _ptr(ii), _ptr(ci), _ptr(io), _ptr(ko), paths,
                            _lib.REGROUP_CELL_OCTANT if box is not None else _lib.REGROUP_KEYS,
                            (C.c_float * 3)(*lo), (C.c_float * 3)(*hi), 0, 0)
-        torch.cuda.current_stream(self._torch_device()).synchronize()
-        check(lib().rt_regroup_paths(self._h, C.byref(g), n), "regroup_paths")
-        self.synchronize()
+        self._query("regroup_paths", lib().rt_regroup_paths, C.byref(g), n)
 
     def trace_wavefront(self, origins, dirs, rng, bounces: int, want_queries: bool = False, regroup_box=None,
                         regroup_after=()):
@@ -763,23 +747,10 @@ class Renderer:
         list changes, the result does not."""
         import torch
 
-        o = self._rays_on_device(origins, "origins").clone()
-        d = self._rays_on_device(dirs, "dirs").clone()
-        if o.shape != d.shape:
-            raise ValueError(f"trace_wavefront: {tuple(o.shape)} origins for {tuple(d.shape)} directions")
-        n = int(o.shape[0])
+        o, d, n = self._ray_pair("trace_wavefront", origins, dirs)
+        o, d = o.clone(), d.clone()
         dev = self._torch_device()
-        s = rng
-        if not torch.is_tensor(s):
-            s = np.asarray(s)
-            if s.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
-                raise ValueError(f"trace_wavefront: rng must be int32 or uint32, got {s.dtype}")
-            s = torch.from_numpy(np.ascontiguousarray(s).view(np.int32)).to(dev)
-        if s.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(s.shape) != (n,):
-            raise ValueError(f"trace_wavefront: rng must be ({n},) int32, got {tuple(s.shape)} {s.dtype}")
-        if s.device != dev:
-            raise ValueError(f"trace_wavefront: rng is on {s.device}, the renderer draws on {dev}")
-        s = s.contiguous().clone()
+        s = self._rng_states("trace_wavefront", rng, n).clone()
         # the sky blend of trace()'s epilogue, one rounded f32 operation per operation of the kernels' expression
         t = d[:, 1] * 0.5 + 0.5
         u = 1.0 - t

@@ -445,7 +445,7 @@ def test_errors():
     assert tuple(r.trace_frame(1000).shape) == (8, 16, 3)
     # the Python layer: shapes, dtypes and devices
     z3 = np.zeros((4, 3), np.float32)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match=r"^trace_rays: origins "):  # (the method's own name, not cast_rays')
         r.trace_rays(np.zeros((4, 2), np.float32), np.zeros((4, 2), np.float32))
     with pytest.raises(ValueError):
         r.trace_rays(z3, np.zeros((5, 3), np.float32))

@@ -41,6 +41,8 @@ hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t
                                    uint32_t* state, hipStream_t stream);
 hipError_t hrt_launch_regroup(const hrt_regroup::Launch& a, uint32_t n, hipStream_t stream);  // rt_regroup.hip
 hipError_t hrt_launch_lbvh(const hrt_lbvh::Launch& a, hipStream_t stream);                     // rt_lbvh.hip
+hipError_t hrt_launch_lbvh_refit(const hrt_lbvh::Refit& a, hipStream_t stream);                // rt_lbvh.hip
+hipError_t hrt_launch_tri_tree_cost(const void* hnodes, uint32_t slots, uint32_t root, uint64_t* out, hipStream_t stream);  // rt_lbvh.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -201,12 +203,17 @@ struct rt_renderer {
     hrt::TriBvh tri_tree;
     DevBuf<uint4> tb_hnodes;
     DevBuf<uint32_t> tb_order;
+    // device geometry only: the parent links of the tree in tb_hnodes (rt_lbvh.hpp Launch::parent, for the bvh_m triangles
+    // it was built over). Part of the tree, not scratch: rt_refit_triangles_device climbs them.
+    DevBuf<uint32_t> tb_parent;
     uint32_t tb_n_nodes = 0, tb_n_order = 0;  // nodes (2 uint4 each) and leaf positions the two buffers hold
     // rt_set_triangles_device: true = device geometry (tris, tri_geo and the tree were made on the device: there is no
     // reference heap and no tri_aee, and every draw and query walks the tree whatever rt_params.tri_bvh says; tri_tree
     // holds only the root word, centre, radius and depth). rt_set_bvh leaves the state.
     bool dev_geom = false;
-    // its staging buffers (a build writes these; success swaps them with tris, tri_geo, mats, tb_hnodes and tb_order, so
+    uint32_t dev_n_mats = 0;  // the materials the device geometry came with (a refit checks the indices against it)
+    // its staging buffers (a build writes these; success swaps them with tris, tri_geo, mats, tb_hnodes, tb_order and
+    // tb_parent (lb_parent is the staging copy of the links); a refit swaps tris, tri_geo and tb_hnodes alone, so
     // they then hold the geometry before: two sets that alternate for a mesh that moves every step) and its scratch
     // (rt_lbvh.hpp Launch): keys and sorted keys, parent links, arrival counters, box slots, the status block
     DevBuf<hrt_dev::TriDev> lb_tris;
@@ -215,6 +222,7 @@ struct rt_renderer {
     DevBuf<uint4> lb_hnodes;
     DevBuf<uint32_t> lb_order, lb_keys, lb_parent, lb_arrivals;
     DevBuf<uint64_t> lb_boxes, lb_stat;
+    uint64_t* refit_stat_host = nullptr;  // pinned: the refit's status read-back lands here (allocated by the first refit)
     DevBuf<unsigned long long> counter;
     DevBuf<unsigned long long> count_spread;  // the work counters' CSPREAD copies (rt_kernels.hip flush_counts)
     DevBuf<unsigned long long> steal_slots;  // sample queue: one word per resident wave (frame-block work stealing)
@@ -273,7 +281,7 @@ struct rt_renderer {
                bvh_sph.bytes() +
                bvh_hnodes.bytes() + bvh_slot.bytes() + bvh_large.bytes() + nodes.bytes() + nodes_so.bytes() + tris.bytes() +
                tri_geo.bytes() + mats.bytes() +
-               tb_hnodes.bytes() + tb_order.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
+               tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
                order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
@@ -1144,6 +1152,9 @@ void delete_buffers(rt_renderer* r) {
     r->mats.release();
     r->tb_hnodes.release();
     r->tb_order.release();
+    r->tb_parent.release();
+    if (r->refit_stat_host) (void)hipHostFree(r->refit_stat_host);
+    r->refit_stat_host = nullptr;
     r->lb_tris.release();
     r->lb_geo.release();
     r->lb_mats.release();
@@ -1409,6 +1420,7 @@ int rt_set_bvh(rt_renderer* r, const uint32_t sizes[2], const void* nodes32, uin
     r->bvh_m = m;
     r->so_ok = so_ok;
     r->dev_geom = false;  // (the heap and tri_aee are back: tri_bvh chooses the walk again)
+    r->tb_parent.release();
     return RT_OK;
 }
 
@@ -1484,11 +1496,13 @@ int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_t
     swap_buffers(r->mats, r->lb_mats);
     swap_buffers(r->tb_hnodes, r->lb_hnodes);
     swap_buffers(r->tb_order, r->lb_order);
+    swap_buffers(r->tb_parent, r->lb_parent);  // (the links belong to the tree: a failed build has not touched the live ones)
     r->tri_tree = std::move(T);
     r->tb_n_nodes = hrt_lbvh::node_slots(finite);
     r->tb_n_order = finite;
     r->tri_tree_dirty = false;
     r->dev_geom = true;
+    r->dev_n_mats = n_mats;
     r->bvh_n = 0;  // no reference heap: nothing reads one in this state (scene_params: tri_bvh)
     r->bvh_m = n_tris;
     r->so_ok = false;
@@ -1524,6 +1538,155 @@ int rt_host_lbvh_build(const void* tris64, uint32_t n_tris, void* hnodes_out, si
     if ((nodes && !hnodes_out) || (!T.order.empty() && !order_out)) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null output");
     if (nodes) std::memcpy(hnodes_out, T.hnodes.data(), nodes * 32u);
     if (!T.order.empty()) std::memcpy(order_out, T.order.data(), T.order.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+// The device tree's boxes for a moved mesh (include/hrt.h; rt_lbvh.hip k_lbvh_refit_prep / _fit). The topology (tb_order,
+// tb_parent, the child words of tb_hnodes) is read and kept; the triangle records and the packed nodes are written to the
+// staging set and swapped in after the status block says the refit is good.
+int rt_refit_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_tris) {
+    if (!r) return fail(RT_ERR_ARG, "rt_refit_triangles_device: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_refit_triangles_device: the sphere program has no triangles");
+    if (n_tris && !tris64_dev) return fail(RT_ERR_ARG, "rt_refit_triangles_device: null triangles");
+    if ((uintptr_t)tris64_dev % 16u) return fail(RT_ERR_ARG, "rt_refit_triangles_device: triangles must be 16-byte aligned");
+    if (!r->dev_geom)
+        return fail(RT_ERR_STATE, "rt_refit_triangles_device: no device geometry to refit (rt_set_triangles_device first)");
+    if (n_tris != r->bvh_m)
+        return fail(RT_ERR_ARG, "rt_refit_triangles_device: n_tris = " + std::to_string(n_tris) + ", the tree was built over " +
+                                    std::to_string(r->bvh_m) + " triangles");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    if (n_tris == 0) {  // (an empty tree stays the empty tree)
+        r->cost_learn = true;
+        return RT_OK;
+    }
+    const size_t n = n_tris;
+    const uint32_t m = r->tb_n_order, slots = hrt_lbvh::node_slots(m);
+    if (m > n_tris || (slots && (!r->tb_parent.ptr || r->tb_parent.cap < 2 * n || r->tb_hnodes.cap < 2 * (size_t)slots ||
+                                 r->tb_order.cap < m)))
+        return fail(RT_ERR_STATE, "rt_refit_triangles_device: the live tree is not consistent");
+    int rc = ensure(r->lb_tris, n);
+    if (!rc) rc = ensure(r->lb_geo, 9 * n);
+    if (!rc) rc = ensure(r->lb_hnodes, 2 * std::max<size_t>(n - 1, 1));
+    if (!rc) rc = ensure(r->lb_stat, hrt_lbvh::STAT_WORDS);
+    if (!rc && slots) rc = ensure(r->lb_arrivals, n);
+    if (!rc && slots) rc = ensure(r->lb_boxes, 2 * n * hrt_lbvh::BOX_WORDS);
+    if (rc) return rc;
+    hrt_lbvh::Refit a{};
+    a.tris64 = tris64_dev;
+    a.n = n_tris;
+    a.n_mats = r->dev_n_mats;
+    a.m = m;
+    a.geo_live = r->tri_geo.ptr;
+    a.hnodes_live = (const hrt_lbvh::U4*)r->tb_hnodes.ptr;
+    a.order = r->tb_order.ptr;
+    a.parent = r->tb_parent.ptr;
+    a.tris_out = r->lb_tris.ptr;
+    a.geo_out = r->lb_geo.ptr;
+    a.hnodes = (hrt_lbvh::U4*)r->lb_hnodes.ptr;
+    a.arrivals = r->lb_arrivals.ptr;
+    a.boxes = r->lb_boxes.ptr;
+    a.stat = r->lb_stat.ptr;
+    // (pinned host memory: the copy is one asynchronous transfer, not a staged one)
+    if (!r->refit_stat_host &&
+        hipHostMalloc((void**)&r->refit_stat_host, hrt_lbvh::STAT_WORDS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
+        r->refit_stat_host = nullptr;
+        return fail(RT_ERR_ALLOC, "rt_refit_triangles_device: hipHostMalloc of the status block failed");
+    }
+    uint64_t* const stat = r->refit_stat_host;
+    HIP_TRY(hrt_launch_lbvh_refit(a, r->stream));
+    HIP_TRY(hipMemcpyAsync(stat, r->lb_stat.ptr, hrt_lbvh::STAT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (stat[7] != 0) return fail(RT_ERR_ARG, "rt_refit_triangles_device: triangle material index out of range");
+    if (stat[9] != 0)
+        return fail(RT_ERR_ARG, "rt_refit_triangles_device: " + std::to_string(stat[9]) +
+                                    " triangles changed between finite and non-finite since the build (build again)");
+    if (stat[6] != m) return fail(RT_ERR_DEVICE, "rt_refit_triangles_device: the refit's status block is not consistent");
+    if (m) {
+        double lo[3], hi[3];
+        for (int k = 0; k < 3; k++) {
+            lo[k] = hrt_lbvh::f64_from_key(~stat[k]);
+            hi[k] = hrt_lbvh::f64_from_key(stat[3 + k]);
+        }
+        hrt_lbvh::root_sphere(lo, hi, r->tri_tree.root_center, &r->tri_tree.root_radius);
+    }
+    if (slots) r->tri_tree.depth = (uint32_t)stat[8];
+    swap_buffers(r->tris, r->lb_tris);
+    swap_buffers(r->tri_geo, r->lb_geo);
+    if (slots) swap_buffers(r->tb_hnodes, r->lb_hnodes);
+    r->cost_learn = true;
+    return RT_OK;
+}
+
+namespace {
+void aee_of_triangles(const void* tris64, uint32_t n_tris, std::vector<float>& aee) {
+    aee.resize(9 * (size_t)n_tris);
+    for (uint32_t j = 0; j < n_tris; j++) {
+        hrt::Triangle t;  // (no alignment asked of the caller)
+        std::memcpy(&t, (const char*)tris64 + 64u * (size_t)j, sizeof t);
+        const float v[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z,
+                            t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
+        std::copy(v, v + 9, &aee[9 * (size_t)j]);
+    }
+}
+}  // namespace
+
+// The refit on the host (rt_lbvh.hpp host_refit: host_build's two halves over two arrays): pure CPU, no device.
+int rt_host_lbvh_refit(const void* tris64_topology, const void* tris64, uint32_t n_tris, void* hnodes_out, size_t hnode_cap,
+                       uint32_t* order_out, size_t order_cap, uint32_t info[8], float root[4]) {
+    if (!info || !root) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: null info or root");
+    if (n_tris && (!tris64_topology || !tris64)) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: null triangles");
+    if (n_tris >= (1u << 26)) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: 2^26 or more triangles");
+    std::vector<float> aee_t, aee;
+    aee_of_triangles(tris64_topology, n_tris, aee_t);
+    aee_of_triangles(tris64, n_tris, aee);
+    hrt_lbvh::HostTree T;
+    if (!hrt_lbvh::host_refit(aee_t.data(), aee.data(), n_tris, T))
+        return fail(RT_ERR_ARG, "rt_host_lbvh_refit: a triangle is finite in one array and not in the other");
+    const size_t nodes = T.hnodes.size() / 2;
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, 0u, 0u, 0u};
+    std::copy(i8, i8 + 8, info);
+    for (int k = 0; k < 3; k++) root[k] = T.rc[k];
+    root[3] = T.radius;
+    if (hnode_cap == 0 && order_cap == 0) return RT_OK;
+    if (hnode_cap < nodes || order_cap < T.order.size()) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: a capacity is too small");
+    if ((nodes && !hnodes_out) || (!T.order.empty() && !order_out)) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: null output");
+    if (nodes) std::memcpy(hnodes_out, T.hnodes.data(), nodes * 32u);
+    if (!T.order.empty()) std::memcpy(order_out, T.order.data(), T.order.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+// The tree cost on the host (rt_lbvh.hpp host_cost): a pure function of the node bytes.
+int rt_host_lbvh_cost(const void* hnodes, size_t node_slots, uint32_t root_word, uint64_t cost[4]) {
+    if (!cost) return fail(RT_ERR_ARG, "rt_host_lbvh_cost: null cost");
+    for (int k = 0; k < 4; k++) cost[k] = 0;
+    if ((root_word & hrt_lbvh::LEAF_BIT) != 0u) return RT_OK;  // a tree without nodes
+    if (root_word >= node_slots) return fail(RT_ERR_ARG, "rt_host_lbvh_cost: the root word names a node past node_slots");
+    if (!hnodes) return fail(RT_ERR_ARG, "rt_host_lbvh_cost: null nodes");
+    std::vector<hrt_lbvh::U4> nodes(2 * node_slots);  // (no alignment asked of the caller)
+    std::memcpy(nodes.data(), hnodes, node_slots * 32u);
+    hrt_lbvh::host_cost(nodes.data(), node_slots, root_word, cost);
+    return RT_OK;
+}
+
+// The same read-out of the tree the renderer walks (rt_lbvh.hip k_tri_tree_cost). Blocking; the four words are summed in
+// the status block's cost words, which no draw reads.
+int rt_get_tri_tree_cost(rt_renderer* r, uint64_t cost[4]) {
+    if (!r || !cost) return fail(RT_ERR_ARG, "rt_get_tri_tree_cost: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_get_tri_tree_cost: the sphere program has no triangle tree");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
+    for (int k = 0; k < 4; k++) cost[k] = 0;
+    const uint32_t root = r->tri_tree.root_word, slots = r->tb_n_nodes;
+    if ((root & hrt_lbvh::LEAF_BIT) != 0u || slots == 0u) return RT_OK;
+    if (root >= slots || r->tb_hnodes.cap < 2 * (size_t)slots)
+        return fail(RT_ERR_STATE, "rt_get_tri_tree_cost: the tree is not consistent");
+    if (int rc = ensure(r->lb_stat, hrt_lbvh::STAT_WORDS)) return rc;
+    uint64_t* const words = r->lb_stat.ptr + 12;
+    HIP_TRY(hrt_launch_tri_tree_cost(r->tb_hnodes.ptr, slots, root, words, r->stream));
+    HIP_TRY(hipMemcpyAsync(cost, words, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }
 
@@ -1981,7 +2144,8 @@ int rt_release_scratch(rt_renderer* r) {
     r->ring_ctl.release();
     r->regroup_entries.release();
     r->regroup_counts.release();
-    // rt_set_triangles_device's scratch and staging (the geometry before the last build), not the tree in use
+    // rt_set_triangles_device's scratch and staging (the geometry before the last build), not the tree in use (tb_parent
+    // is the tree's: a refit after this call allocates staging, arrivals and boxes again)
     r->lb_tris.release();
     r->lb_geo.release();
     r->lb_mats.release();

@@ -20,6 +20,9 @@
 //   fit       the f64 box of a node is the union of its children's; a referenced node's two child boxes are packed as
 //             the host's SAH tree packs them (pack_child: down / up to f32 with the extra ulp, relative to the f32 root
 //             centre with one more ulp outward, fp16 outward).
+//   refit     (rt_refit_triangles_device, rt_host_lbvh_refit) prep and fit over another array of the same triangles, on
+//             the topology as it stands: the same set of finite triangles is asked for, nothing else.
+//   cost      (rt_get_tri_tree_cost, rt_host_lbvh_cost) cost_node: integers from the packed boxes alone.
 #pragma once
 #include <stdint.h>
 
@@ -216,9 +219,62 @@ HRT_LBVH_FN uint32_t root_word(uint32_t m) { return m <= LEAF_MAX ? (LEAF_BIT | 
 // Internal nodes the hnode array holds (referenced or not) for m finite triangles.
 HRT_LBVH_FN uint32_t node_slots(uint32_t m) { return m <= LEAF_MAX ? 0u : m - 1u; }
 
+// ---- tree cost (rt_get_tri_tree_cost, rt_host_lbvh_cost) ----
+// A pure function of a tree's bytes, in integers: per child of a referenced node the half-area of its decoded fp16 box over
+// the half-area R of the root node's two children's union, as a 16.16 fixed-point number. Any tree of the node format.
+// One extent of a packed box: hi - lo of the two halves (exact in f64); nothing for an empty or NaN extent, and the
+// largest extent two finite halves have for anything beyond it (inf halves).
+HRT_LBVH_FN double cost_extent(uint32_t word) {
+    const double lo = (double)f16_from_bits((uint16_t)(word & 0xFFFFu)), hi = (double)f16_from_bits((uint16_t)(word >> 16));
+    const double e = hi - lo;
+    if (!(e > 0.0)) return 0.0;
+    return e > 131008.0 ? 131008.0 : e;
+}
+HRT_LBVH_FN double cost_half_area(double ex, double ey, double ez) {
+    const double xy = ex * ey, yz = ey * ez, zx = ez * ex;  // (each rounded: no FMA)
+    const double s = xy + yz;
+    return s + zx;
+}
+HRT_LBVH_FN double cost_child_area(const U4& c) { return cost_half_area(cost_extent(c.x), cost_extent(c.y), cost_extent(c.z)); }
+// R: the same expression over the union of the root node's two child boxes.
+HRT_LBVH_FN double cost_root_area(const U4& l, const U4& r) {
+    const uint32_t a[3] = {l.x, l.y, l.z}, b[3] = {r.x, r.y, r.z};
+    double e[3];
+    for (int k = 0; k < 3; k++) {
+        const double lo = dmin((double)f16_from_bits((uint16_t)(a[k] & 0xFFFFu)), (double)f16_from_bits((uint16_t)(b[k] & 0xFFFFu)));
+        const double hi = dmax((double)f16_from_bits((uint16_t)(a[k] >> 16)), (double)f16_from_bits((uint16_t)(b[k] >> 16)));
+        const double d = hi - lo;
+        e[k] = !(d > 0.0) ? 0.0 : d > 131008.0 ? 131008.0 : d;
+    }
+    return cost_half_area(e[0], e[1], e[2]);
+}
+HRT_LBVH_FN uint64_t cost_q(double A, double R) {
+    if (!(R > 0.0)) return 0u;
+    const double v = A / R * 65536.0;  // (A, R finite and >= 0: never NaN)
+    return v >= 4294967296.0 ? 4294967296ull : (uint64_t)v;
+}
+// One node slot's share: cost[0] q of node children, [1] q x count of leaf children, [2] referenced nodes, [3] leaf entries.
+HRT_LBVH_FN void cost_node(const U4& l, const U4& r, double R, uint64_t cost[4]) {
+    if (l.w == 0u) return;  // a slot no child word names
+    cost[2] += 1u;
+    const U4* const c[2] = {&l, &r};
+    for (int s = 0; s < 2; s++) {
+        const uint64_t q = cost_q(cost_child_area(*c[s]), R);
+        if ((c[s]->w & LEAF_BIT) != 0u) {
+            const uint64_t count = c[s]->w & 15u;
+            cost[1] += q * count;
+            cost[3] += count;
+        } else {
+            cost[0] += q;
+        }
+    }
+}
+
 // ---- the device build's memory (rt_lbvh.hip; renderer.cpp allocates) ----
 constexpr uint32_t STAT_WORDS = 16;  // u64 each: [0..2] ~f64_key of the root minima, [3..5] f64_key of the root maxima,
-                                     // [6] finite triangles, [7] triangles with a bad material index, [8] depth
+                                     // [6] finite triangles, [7] triangles with a bad material index, [8] depth,
+                                     // [9] (refit) triangles whose finiteness is not the live tree's,
+                                     // [12..15] (rt_get_tri_tree_cost) the four cost words
 constexpr uint32_t BOX_WORDS = 8;    // u64 per (node, side): lo xyz, hi xyz as f64 bits, the subtree's height, unused
 struct Launch {
     const void* tris64;       // the caller's n Triangle records (device)
@@ -235,6 +291,21 @@ struct Launch {
     uint64_t* stat;           // STAT_WORDS
     uint32_t* sort_entries;   // the renderer's regroup scratch (rt_regroup.hpp Launch)
     uint32_t* sort_counts;
+};
+// rt_refit_triangles_device: the live tree's topology is read, the staging set is written (k_lbvh_refit_prep, _fit).
+struct Refit {
+    const void* tris64;          // the caller's n Triangle records (device)
+    uint32_t n, n_mats, m;       // m: the live tree's finite triangles (leaf positions)
+    const float* geo_live;       // 9 n floats: the live tri_geo, for the finiteness comparison
+    const U4* hnodes_live;       // the live node array: the child words
+    const uint32_t* order;       // m: the live sorted triangle indices
+    const uint32_t* parent;      // 2 n: the live parent links, laid out as Launch::parent
+    void* tris_out;              // staging: n TriDev
+    float* geo_out;              // staging: 9 n floats
+    U4* hnodes;                  // staging: 2 (m - 1) entries, zeroed per call (by the prep)
+    uint32_t* arrivals;          // n, the first m - 1 zeroed per call (by the prep)
+    uint64_t* boxes;             // 2 n BOX_WORDS
+    uint64_t* stat;              // STAT_WORDS, zeroed per call
 };
 
 // ---- the builder on the host ----
@@ -257,32 +328,38 @@ inline void root_sphere(const double lo[3], const double hi[3], float rc[3], flo
     *radius = f32_outward(std::sqrt(diag2) * (1.0 + 1e-6), true);
 }
 
+// The build in two halves, so that the refit (rt_host_lbvh_refit) shares them: host_topology is everything that depends on
+// the keys (which triangles are in the tree, their order, the parent links, the child words), host_fit everything that
+// depends on positions alone (the root sphere, the packed boxes, the depth).
+struct HostTopology {
+    std::vector<uint8_t> fin;     // per triangle: in the tree
+    std::vector<uint32_t> order;  // the finite triangles' indices in key order
+    std::vector<uint32_t> parent; // 2 m: of internal node i at [i], of sorted position p at [m + p]: node << 1 | side
+    std::vector<U4> words;        // 2 per node slot: only the child words (w) of the referenced nodes are set
+    uint32_t finite = 0;
+};
+
 // aee: 9 floats per triangle (a, e1, e2), as rt_set_bvh and the prep kernel make them.
-inline HostTree host_build(const float* aee, uint32_t n) {
-    HostTree T;
-    struct Box {
-        double lo[3], hi[3];
-    };
-    std::vector<Box> tb(n);
+inline HostTopology host_topology(const float* aee, uint32_t n) {
+    HostTopology P;
     std::vector<uint32_t> keys(n, KEY_NONFINITE);
-    std::vector<uint8_t> fin(n, 0);
+    P.fin.assign(n, 0);
     double rlo[3] = {INFINITY, INFINITY, INFINITY}, rhi[3] = {-INFINITY, -INFINITY, -INFINITY};
     std::vector<double> cen(3 * (size_t)n);
     for (uint32_t j = 0; j < n; j++) {
-        if (!tri_bounds(aee + 9 * (size_t)j, tb[j].lo, tb[j].hi, &cen[3 * (size_t)j])) continue;
-        fin[j] = 1;
-        T.finite++;
+        double lo[3], hi[3];
+        if (!tri_bounds(aee + 9 * (size_t)j, lo, hi, &cen[3 * (size_t)j])) continue;
+        P.fin[j] = 1;
+        P.finite++;
         for (int k = 0; k < 3; k++) {
-            rlo[k] = dmin(rlo[k], tb[j].lo[k]);
-            rhi[k] = dmax(rhi[k], tb[j].hi[k]);
+            rlo[k] = dmin(rlo[k], lo[k]);
+            rhi[k] = dmax(rhi[k], hi[k]);
         }
     }
-    const uint32_t m = T.finite;
-    T.root = root_word(m);
-    if (m == 0) return T;
-    root_sphere(rlo, rhi, T.rc, &T.radius);
+    const uint32_t m = P.finite;
+    if (m == 0) return P;
     for (uint32_t j = 0; j < n; j++)
-        if (fin[j]) keys[j] = morton_key(&cen[3 * (size_t)j], rlo, rhi);
+        if (P.fin[j]) keys[j] = morton_key(&cen[3 * (size_t)j], rlo, rhi);
     // stable counting sort by key, 4 passes of 8 bits (any stable sort gives this order)
     std::vector<uint32_t> idx(n), tmp(n);
     for (uint32_t j = 0; j < n; j++) idx[j] = j;
@@ -293,25 +370,56 @@ inline HostTree host_build(const float* aee, uint32_t n) {
         for (uint32_t i = 0; i < n; i++) tmp[count[(keys[idx[i]] >> shift) & 255u]++] = idx[i];
         idx.swap(tmp);
     }
-    T.order.assign(idx.begin(), idx.begin() + m);
-    if (m <= LEAF_MAX) return T;
+    P.order.assign(idx.begin(), idx.begin() + m);
+    if (m <= LEAF_MAX) return P;
     std::vector<uint32_t> ks(m);
-    for (uint32_t p = 0; p < m; p++) ks[p] = keys[T.order[p]];
+    for (uint32_t p = 0; p < m; p++) ks[p] = keys[P.order[p]];
     const uint32_t nodes = m - 1u;
-    T.hnodes.assign(2 * (size_t)nodes, U4{0u, 0u, 0u, 0u});
-    std::vector<uint32_t> parent(2 * (size_t)m, NO_PARENT);
+    P.words.assign(2 * (size_t)nodes, U4{0u, 0u, 0u, 0u});
+    P.parent.assign(2 * (size_t)m, NO_PARENT);
     for (uint32_t i = 0; i < nodes; i++) {
         int first, last, split;
         topology(ks.data(), (int)m, (int)i, first, last, split);
-        if (split == first) parent[m + (uint32_t)split] = i << 1;
-        else parent[(uint32_t)split] = i << 1;
-        if (split + 1 == last) parent[m + (uint32_t)split + 1u] = i << 1 | 1u;
-        else parent[(uint32_t)split + 1u] = i << 1 | 1u;
+        if (split == first) P.parent[m + (uint32_t)split] = i << 1;
+        else P.parent[(uint32_t)split] = i << 1;
+        if (split + 1 == last) P.parent[m + (uint32_t)split + 1u] = i << 1 | 1u;
+        else P.parent[(uint32_t)split + 1u] = i << 1 | 1u;
         if ((uint32_t)(last - first + 1) > LEAF_MAX) {
-            T.hnodes[2 * (size_t)i].w = child_word(first, split, split);
-            T.hnodes[2 * (size_t)i + 1].w = child_word(split + 1, last, split + 1);
+            P.words[2 * (size_t)i].w = child_word(first, split, split);
+            P.words[2 * (size_t)i + 1].w = child_word(split + 1, last, split + 1);
         }
     }
+    return P;
+}
+
+// The boxes of `aee` on the topology P (of the same n triangles). False, with T untouched past its defaults, when a
+// triangle of aee is finite where P's was not or the other way round.
+inline bool host_fit(const HostTopology& P, const float* aee, uint32_t n, HostTree& T) {
+    struct Box {
+        double lo[3], hi[3];
+    };
+    std::vector<Box> tb(n);
+    double rlo[3] = {INFINITY, INFINITY, INFINITY}, rhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t j = 0; j < n; j++) {
+        double cen[3];
+        const bool fin = tri_bounds(aee + 9 * (size_t)j, tb[j].lo, tb[j].hi, cen);
+        if (fin != (P.fin[j] != 0)) return false;
+        if (!fin) continue;
+        for (int k = 0; k < 3; k++) {
+            rlo[k] = dmin(rlo[k], tb[j].lo[k]);
+            rhi[k] = dmax(rhi[k], tb[j].hi[k]);
+        }
+    }
+    const uint32_t m = P.finite;
+    T.finite = m;
+    T.root = root_word(m);
+    if (m == 0) return true;
+    root_sphere(rlo, rhi, T.rc, &T.radius);
+    T.order = P.order;
+    if (m <= LEAF_MAX) return true;
+    const uint32_t nodes = m - 1u;
+    T.hnodes = P.words;
+    const std::vector<uint32_t>& parent = P.parent;
     // the fit, as the device does it: every position climbs; at a parent the first arriver leaves its box and stops
     struct Side {
         Box b;
@@ -342,7 +450,26 @@ inline HostTree host_build(const float* aee, uint32_t n) {
             link = parent[node];
         }
     }
+    return true;
+}
+
+inline HostTree host_build(const float* aee, uint32_t n) {
+    HostTree T;
+    host_fit(host_topology(aee, n), aee, n, T);  // (never false: the same array)
     return T;
+}
+
+// Topology of aee_topology, boxes of aee (rt_host_lbvh_refit). False for a finiteness mismatch.
+inline bool host_refit(const float* aee_topology, const float* aee, uint32_t n, HostTree& T) {
+    return host_fit(host_topology(aee_topology, n), aee, n, T);
+}
+
+// The cost read-out on the host: every node slot, in any order (the sums are of integers).
+inline void host_cost(const U4* hnodes, size_t node_slots, uint32_t root, uint64_t cost[4]) {
+    for (int k = 0; k < 4; k++) cost[k] = 0;
+    if ((root & LEAF_BIT) != 0u || (size_t)root >= node_slots) return;
+    const double R = cost_root_area(hnodes[2 * (size_t)root], hnodes[2 * (size_t)root + 1]);
+    for (size_t i = 0; i < node_slots; i++) cost_node(hnodes[2 * i], hnodes[2 * i + 1], R, cost);
 }
 
 }  // namespace hrt_lbvh

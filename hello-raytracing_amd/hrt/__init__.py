@@ -9,7 +9,7 @@ from ._lib import (REGROUP_CELL_OCTANT, REGROUP_KEYS, REGROUP_TILE, RtRegroup, R
 from .scene import (CAMERA_DTYPE, HIT_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
                     Renderer, SceneSphere, SceneTris, Sphere, Tree, Vec3, compare_ppm_images, f32,
-                    lbvh_build, ppm_from_image, read_asset, render_ppm, spheres_array)
+                    lbvh_build, lbvh_cost, lbvh_refit, ppm_from_image, read_asset, render_ppm, spheres_array)
 
 
 def device_count() -> int:
@@ -103,5 +103,5 @@ __all__ = [
     "SceneSphere", "SceneTris", "Sphere", "Tree", "Vec3", "compare_ppm_images", "f32", "ppm_from_image",
     "read_asset", "render_ppm", "spheres_array", "device_count", "check_uniform_guards", "UGUARD_COLUMNS", "UGUARD_HELPERS",
     "sphere_bvh_leaves", "regroup_keys", "REGROUP_CELL_OCTANT", "REGROUP_KEYS", "REGROUP_TILE", "RtRegroup",
-    "lbvh_build",
+    "lbvh_build", "lbvh_refit", "lbvh_cost",
 ]

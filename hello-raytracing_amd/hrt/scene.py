@@ -347,23 +347,47 @@ class Renderer:
         (m, 64) uint8 in the layout of TRIANGLE_DTYPE, with an LBVH built for them on the GPU; materials as in write_bvh
         (numpy). The renderer then has device geometry: every draw and query walks that tree (include/hrt.h).
         Synchronises torch's current stream before the call; the call itself is synchronous."""
+        stream = self._check_device_triangles(tris, "set_triangles_device")
+        materials = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
+        stream.synchronize()
+        check(lib().rt_set_triangles_device(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0]),
+                                            materials.ctypes.data, len(materials)), "set_triangles_device")
+
+    def _check_device_triangles(self, tris, where: str):
+        """The tensor checks of set_triangles_device / refit_triangles_device; returns torch's current stream on the
+        renderer's device, for the caller to synchronise."""
         import torch
 
         dev = self._torch_device()
         if not torch.is_tensor(tris):
-            raise TypeError("set_triangles_device: tris must be a torch tensor on the renderer's device")
+            raise TypeError(f"{where}: tris must be a torch tensor on the renderer's device")
         if tris.device != dev:
-            raise ValueError(f"set_triangles_device: tris is on {tris.device}, the renderer draws on {dev}")
+            raise ValueError(f"{where}: tris is on {tris.device}, the renderer draws on {dev}")
         if not ((tris.dtype == torch.float32 and tris.ndim == 2 and tris.shape[1] == 16) or
                 (tris.dtype == torch.uint8 and tris.ndim == 2 and tris.shape[1] == 64)):
-            raise ValueError(f"set_triangles_device: tris must be (m, 16) float32 or (m, 64) uint8, got "
+            raise ValueError(f"{where}: tris must be (m, 16) float32 or (m, 64) uint8, got "
                              f"{tuple(tris.shape)} {tris.dtype}")
         if not tris.is_contiguous():
-            raise ValueError("set_triangles_device: tris must be contiguous")
-        materials = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
-        torch.cuda.current_stream(dev).synchronize()
-        check(lib().rt_set_triangles_device(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0]),
-                                            materials.ctypes.data, len(materials)), "set_triangles_device")
+            raise ValueError(f"{where}: tris must be contiguous")
+        return torch.cuda.current_stream(dev)
+
+    def refit_triangles_device(self, tris) -> None:
+        """rt_refit_triangles_device: the moved positions of the mesh of the last set_triangles_device (same tensor
+        layout, same count), on that build's topology: only the triangle records and the boxes are made again. Hits are
+        bit for bit a fresh build's; the tree gets slower as the mesh leaves the built pose (tri_tree_cost()).
+        Synchronises torch's current stream before the call; the call itself is synchronous."""
+        stream = self._check_device_triangles(tris, "refit_triangles_device")
+        stream.synchronize()
+        check(lib().rt_refit_triangles_device(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0])),
+              "refit_triangles_device")
+
+    def tri_tree_cost(self) -> np.ndarray:
+        """rt_get_tri_tree_cost: four uint64 of the triangle tree the renderer walks (device geometry, or tri_bvh = 1):
+        q of node children, q x count of leaf children (q: box half-area over the root's, x 65536), referenced nodes,
+        leaf entries. (cost[0] + cost[1]) / 65536 is the usual SAH figure; hrt.lbvh_cost is the same on the host."""
+        cost = (C.c_uint64 * 4)()
+        check(lib().rt_get_tri_tree_cost(self._h, cost), "tri_tree_cost")
+        return np.array(list(cost), dtype=np.uint64)
 
     def tri_tree(self) -> dict:
         """Test-only (include/hrt_testing.h rt_testing_get_tri_tree): the triangle tree the renderer walks, read back, in
@@ -822,6 +846,35 @@ def lbvh_build(triangles: np.ndarray) -> dict:
         t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 16)
     m, p = len(t), t.ctypes.data
     return _tree_dict(lambda *a: lib().rt_host_lbvh_build(p if m else None, m, *a), "rt_host_lbvh_build")
+
+
+def _triangle_records(triangles: np.ndarray) -> np.ndarray:
+    t = np.ascontiguousarray(triangles)
+    if t.dtype != TRIANGLE_DTYPE:
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 16)
+    return t
+
+
+def lbvh_refit(topology_triangles: np.ndarray, triangles: np.ndarray) -> dict:
+    """rt_host_lbvh_refit (include/hrt.h): rt_refit_triangles_device on the host, no device. The tree has the topology
+    lbvh_build gives topology_triangles and the boxes of triangles (the same count; a triangle finite in one array and
+    not in the other is an RtError). The dict is lbvh_build's."""
+    a, b = _triangle_records(topology_triangles), _triangle_records(triangles)
+    if len(a) != len(b):
+        raise ValueError(f"lbvh_refit: {len(a)} triangles for the topology, {len(b)} to fit")
+    m, pa, pb = len(a), a.ctypes.data, b.ctypes.data
+    return _tree_dict(lambda *x: lib().rt_host_lbvh_refit(pa if m else None, pb if m else None, m, *x), "rt_host_lbvh_refit")
+
+
+def lbvh_cost(tree: dict) -> np.ndarray:
+    """rt_host_lbvh_cost (include/hrt.h): the four uint64 cost words of a tree dict (lbvh_build, lbvh_refit,
+    Renderer.tri_tree): a pure function of the node bytes and the root word. Renderer.tri_tree_cost is the same on the
+    device."""
+    nodes = np.ascontiguousarray(tree["nodes"], dtype=np.uint32).reshape(-1, 8)
+    cost = (C.c_uint64 * 4)()
+    check(lib().rt_host_lbvh_cost(nodes.ctypes.data if len(nodes) else None, len(nodes), int(tree["info"][3]), cost),
+          "rt_host_lbvh_cost")
+    return np.array(list(cost), dtype=np.uint64)
 
 
 def render_ppm(renderer: Renderer) -> str:

@@ -238,6 +238,47 @@ int rt_set_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_t
  * always written. With both capacities 0 only they are returned; a capacity that is too small otherwise is RT_ERR_ARG. */
 int rt_host_lbvh_build(const void *tris64, uint32_t n_tris, void *hnodes_out, size_t hnode_cap, uint32_t *order_out,
                        size_t order_cap, uint32_t info[8], float root[4]);
+/* Refit: the moved positions of a mesh that keeps its connectivity, on the tree of the last successful
+ * rt_set_triangles_device. tris64_dev: the same records as there (64 B each, device memory on the renderer's GPU, 16-byte
+ * aligned); n_tris must equal that build's count. Kept: the build's topology, that is the sorted order, the parent links
+ * and every child word, so a leaf holds the triangle indices it held. Recomputed with the build's own rules, from the array
+ * given now: the kernels' triangle records (custom normal and material index included), the per-triangle f64 boxes, the
+ * root box, centre and radius, every referenced node's two packed child boxes (relative to the NEW root centre), the
+ * depth (which comes out the same). The materials table is not touched: a material index >= the count given to the build
+ * is an error. A tree without nodes (<= 4 finite triangles) changes only its triangle records and root sphere.
+ * The refitted tree is a pure function of two arrays: the topology of the array of the last successful build, the boxes of
+ * the array given now. build(A), refit(B), refit(C) leaves the bytes of rt_host_lbvh_refit(A, C); a refit with the
+ * unmoved array leaves the build's bytes. The hit contract does not depend on the tree's shape: every query and draw
+ * returns bit for bit what a fresh rt_set_triangles_device on the new array returns; only the speed may differ, and it
+ * gets worse as the mesh leaves the pose the tree was built for (rt_get_tri_tree_cost says how much; the caller decides
+ * when to build again). One memset, two kernels and the status read-back: no keys, no sort, no topology.
+ * RT_ERR_ARG: the sphere program; a null tris64_dev with n_tris > 0; a pointer that is not 16-byte aligned; n_tris other
+ * than the built count; a material index out of range; a triangle that changed finiteness either way (the set of
+ * triangles with a non-finite a, e1 or e2 must be the one the topology was built over; counted on the device, the
+ * message has the count). RT_ERR_STATE: no device geometry (never set, or rt_set_bvh left the state). On any failure the
+ * renderer keeps the geometry it had: the refit writes the staging set and swaps it in on success. The parent links are
+ * part of the tree (counted in rt_stats.device_bytes, kept by rt_release_scratch, untouched by a build that fails): a
+ * refit after rt_release_scratch allocates staging and scratch again, a refit after a failed build uses the live tree.
+ * Synchronous on the renderer's stream like the build; drops the learnt cost order; image, frame count and rt_get_stats
+ * are not touched. */
+int rt_refit_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_tris);
+/* The refit on the host: the topology rt_host_lbvh_build gives tris64_topology, the boxes of tris64 (n_tris records each,
+ * host memory). Outputs, capacities and the two-call protocol are rt_host_lbvh_build's. RT_ERR_ARG also when a triangle
+ * is finite in one array and not in the other. rt_host_lbvh_refit(A, A) is rt_host_lbvh_build(A). */
+int rt_host_lbvh_refit(const void *tris64_topology, const void *tris64, uint32_t n_tris, void *hnodes_out,
+                       size_t hnode_cap, uint32_t *order_out, size_t order_cap, uint32_t info[8], float root[4]);
+/* Tree cost: a deterministic read-out of any tree in the node format above (the host SAH tree of tri_bvh = 1 included),
+ * in integers, so that no summation order can matter; a pure function of the bytes. A referenced node is a slot whose left
+ * child word is not 0. Per child of one: the six halves decoded to f64; per axis e = hi - lo, 0 if !(e > 0), 131008 if
+ * e > 131008 (inf halves); A = e_x e_y + e_y e_z + e_z e_x, products and sums rounded in that order, no FMA. R is the same
+ * expression over the union of the two child boxes of the node root_word names. q = R > 0 ? min((uint64_t)(A / R *
+ * 65536.0), 2^32) : 0 (IEEE division). cost[0] = sum of q over children that are nodes; cost[1] = sum of q x count over
+ * leaf children; cost[2] = referenced nodes; cost[3] = leaf entries (sum of count). A root word that is a leaf gives four
+ * zeros. The usual SAH figure is (cost[0] + cost[1]) / 65536. RT_ERR_ARG: a root word that names a node >= node_slots. */
+int rt_host_lbvh_cost(const void *hnodes, size_t node_slots, uint32_t root_word, uint64_t cost[4]);
+/* The same read-out, by a small kernel, of the tree the renderer walks with tri_bvh = 1 or with device geometry (a host
+ * SAH tree not built yet is built first). Blocking. RT_ERR_ARG in the sphere program. Touches nothing a draw reads. */
+int rt_get_tri_tree_cost(rt_renderer *r, uint64_t cost[4]);
 
 /* Renderer::set_time / set_frame_count — renderer.rs:315-323. */
 int rt_set_time(rt_renderer *r, uint32_t time);
@@ -526,8 +567,9 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
 #define RT_ABI_VERSION 7u /* 7: rt_check_uniform_guards (no struct change); 6: rt_params.packet (round 6);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
                              rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, then rt_regroup_paths /
-                             rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, came later without a
-                             new version (no struct changed): detect them by their symbols */
+                             rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, then
+                             rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, came
+                             later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 
 /* Thread-local message for the last failing call. */

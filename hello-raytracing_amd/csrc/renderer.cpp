@@ -42,6 +42,7 @@ hipError_t hrt_launch_primary_rays(int mode, const hrt_dev::KParams& P, uint32_t
 hipError_t hrt_launch_regroup(const hrt_regroup::Launch& a, uint32_t n, hipStream_t stream);  // rt_regroup.hip
 hipError_t hrt_launch_lbvh(const hrt_lbvh::Launch& a, hipStream_t stream);                     // rt_lbvh.hip
 hipError_t hrt_launch_lbvh_refit(const hrt_lbvh::Refit& a, hipStream_t stream);                // rt_lbvh.hip
+hipError_t hrt_launch_lbvh_ploc(const hrt_lbvh::Launch& a, uint64_t* pinned, hipStream_t stream);  // rt_ploc.hip
 hipError_t hrt_launch_tri_tree_cost(const void* hnodes, uint32_t slots, uint32_t root, uint64_t* out, hipStream_t stream);  // rt_lbvh.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
@@ -207,6 +208,8 @@ struct rt_renderer {
     // it was built over). Part of the tree, not scratch: rt_refit_triangles_device climbs them.
     DevBuf<uint32_t> tb_parent;
     uint32_t tb_n_nodes = 0, tb_n_order = 0;  // nodes (2 uint4 each) and leaf positions the two buffers hold
+    // device geometry only (rt_get_tri_tree_info): the builder of the tree in tb_hnodes, and PLOC's iteration counts
+    uint32_t tb_builder = RT_TREE_LBVH, tb_iterations = 0, tb_flat = 0;
     // rt_set_triangles_device: true = device geometry (tris, tri_geo and the tree were made on the device: there is no
     // reference heap and no tri_aee, and every draw and query walks the tree whatever rt_params.tri_bvh says; tri_tree
     // holds only the root word, centre, radius and depth). rt_set_bvh leaves the state.
@@ -222,7 +225,8 @@ struct rt_renderer {
     DevBuf<uint4> lb_hnodes;
     DevBuf<uint32_t> lb_order, lb_keys, lb_parent, lb_arrivals;
     DevBuf<uint64_t> lb_boxes, lb_stat;
-    uint64_t* refit_stat_host = nullptr;  // pinned: the refit's status read-back lands here (allocated by the first refit)
+    // pinned: the status read-backs of the refit and of the PLOC build land here (allocated by the first of them)
+    uint64_t* refit_stat_host = nullptr;
     DevBuf<unsigned long long> counter;
     DevBuf<unsigned long long> count_spread;  // the work counters' CSPREAD copies (rt_kernels.hip flush_counts)
     DevBuf<unsigned long long> steal_slots;  // sample queue: one word per resident wave (frame-block work stealing)
@@ -1427,7 +1431,15 @@ int rt_set_bvh(rt_renderer* r, const uint32_t sizes[2], const void* nodes32, uin
 // Triangles from device memory, with an LBVH built for them on the device (include/hrt.h; rt_lbvh.hip, rt_lbvh.hpp).
 // Everything is written to the staging buffers and swapped in after the status block says the build is good.
 int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_tris, const void* mats32, uint32_t n_mats) {
+    return rt_set_triangles_device_with(r, tris64_dev, n_tris, mats32, n_mats, RT_TREE_LBVH);
+}
+
+// builder: RT_TREE_LBVH (Karras' topology, k_lbvh_topology) or RT_TREE_PLOC (rt_ploc.hip); everything around it is shared.
+int rt_set_triangles_device_with(rt_renderer* r, const void* tris64_dev, uint32_t n_tris, const void* mats32, uint32_t n_mats,
+                                 uint32_t builder) {
     if (!r) return fail(RT_ERR_ARG, "rt_set_triangles_device: null");
+    if (builder != RT_TREE_LBVH && builder != RT_TREE_PLOC)
+        return fail(RT_ERR_ARG, "rt_set_triangles_device: unknown builder " + std::to_string(builder));
     if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_set_triangles_device: the sphere program has no triangles");
     if (n_tris && !tris64_dev) return fail(RT_ERR_ARG, "rt_set_triangles_device: null triangles");
     if ((uintptr_t)tris64_dev % 16u) return fail(RT_ERR_ARG, "rt_set_triangles_device: triangles must be 16-byte aligned");
@@ -1471,7 +1483,17 @@ int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_t
         a.stat = r->lb_stat.ptr;
         a.sort_entries = r->regroup_entries.ptr;
         a.sort_counts = r->regroup_counts.ptr;
-        HIP_TRY(hrt_launch_lbvh(a, r->stream));
+        if (builder == RT_TREE_PLOC) {
+            // (pinned host memory: the builder reads a cluster count back per iteration)
+            if (!r->refit_stat_host && hipHostMalloc((void**)&r->refit_stat_host, hrt_lbvh::STAT_WORDS * sizeof(uint64_t),
+                                                     hipHostMallocDefault) != hipSuccess) {
+                r->refit_stat_host = nullptr;
+                return fail(RT_ERR_ALLOC, "rt_set_triangles_device: hipHostMalloc of the status block failed");
+            }
+            HIP_TRY(hrt_launch_lbvh_ploc(a, r->refit_stat_host, r->stream));
+        } else {
+            HIP_TRY(hrt_launch_lbvh(a, r->stream));
+        }
         HIP_TRY(hipMemcpyAsync(stat, r->lb_stat.ptr, sizeof stat, hipMemcpyDeviceToHost, r->stream));
     }
     if (n_mats)
@@ -1500,6 +1522,10 @@ int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_t
     r->tri_tree = std::move(T);
     r->tb_n_nodes = hrt_lbvh::node_slots(finite);
     r->tb_n_order = finite;
+    r->tb_builder = builder;
+    const bool ploc_nodes = builder == RT_TREE_PLOC && hrt_lbvh::node_slots(finite) != 0u;
+    r->tb_iterations = ploc_nodes ? (uint32_t)stat[10] : 0u;
+    r->tb_flat = ploc_nodes ? (uint32_t)stat[11] : 0u;
     r->tri_tree_dirty = false;
     r->dev_geom = true;
     r->dev_n_mats = n_mats;
@@ -1516,7 +1542,14 @@ int rt_set_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n_t
 // The builder on the host (rt_lbvh.hpp host_build): pure CPU, no device.
 int rt_host_lbvh_build(const void* tris64, uint32_t n_tris, void* hnodes_out, size_t hnode_cap, uint32_t* order_out,
                        size_t order_cap, uint32_t info[8], float root[4]) {
+    return rt_host_lbvh_build_with(tris64, n_tris, RT_TREE_LBVH, hnodes_out, hnode_cap, order_out, order_cap, info, root);
+}
+
+int rt_host_lbvh_build_with(const void* tris64, uint32_t n_tris, uint32_t builder, void* hnodes_out, size_t hnode_cap,
+                            uint32_t* order_out, size_t order_cap, uint32_t info[8], float root[4]) {
     if (!info || !root) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null info or root");
+    if (builder != RT_TREE_LBVH && builder != RT_TREE_PLOC)
+        return fail(RT_ERR_ARG, "rt_host_lbvh_build: unknown builder " + std::to_string(builder));
     if (n_tris && !tris64) return fail(RT_ERR_ARG, "rt_host_lbvh_build: null triangles");
     if (n_tris >= (1u << 26)) return fail(RT_ERR_ARG, "rt_host_lbvh_build: 2^26 or more triangles");
     std::vector<float> aee(9 * (size_t)n_tris);
@@ -1527,9 +1560,9 @@ int rt_host_lbvh_build(const void* tris64, uint32_t n_tris, void* hnodes_out, si
                             t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
         std::copy(v, v + 9, &aee[9 * (size_t)j]);
     }
-    const hrt_lbvh::HostTree T = hrt_lbvh::host_build(aee.data(), n_tris);
+    const hrt_lbvh::HostTree T = hrt_lbvh::host_build(aee.data(), n_tris, builder);
     const size_t nodes = T.hnodes.size() / 2;
-    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, 0u, 0u, 0u};
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, T.iterations, T.flat, 0u};
     std::copy(i8, i8 + 8, info);
     for (int k = 0; k < 3; k++) root[k] = T.rc[k];
     root[3] = T.radius;
@@ -1634,17 +1667,25 @@ void aee_of_triangles(const void* tris64, uint32_t n_tris, std::vector<float>& a
 // The refit on the host (rt_lbvh.hpp host_refit: host_build's two halves over two arrays): pure CPU, no device.
 int rt_host_lbvh_refit(const void* tris64_topology, const void* tris64, uint32_t n_tris, void* hnodes_out, size_t hnode_cap,
                        uint32_t* order_out, size_t order_cap, uint32_t info[8], float root[4]) {
+    return rt_host_lbvh_refit_with(tris64_topology, tris64, n_tris, RT_TREE_LBVH, hnodes_out, hnode_cap, order_out, order_cap, info,
+                                   root);
+}
+
+int rt_host_lbvh_refit_with(const void* tris64_topology, const void* tris64, uint32_t n_tris, uint32_t builder, void* hnodes_out,
+                            size_t hnode_cap, uint32_t* order_out, size_t order_cap, uint32_t info[8], float root[4]) {
     if (!info || !root) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: null info or root");
+    if (builder != RT_TREE_LBVH && builder != RT_TREE_PLOC)
+        return fail(RT_ERR_ARG, "rt_host_lbvh_refit: unknown builder " + std::to_string(builder));
     if (n_tris && (!tris64_topology || !tris64)) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: null triangles");
     if (n_tris >= (1u << 26)) return fail(RT_ERR_ARG, "rt_host_lbvh_refit: 2^26 or more triangles");
     std::vector<float> aee_t, aee;
     aee_of_triangles(tris64_topology, n_tris, aee_t);
     aee_of_triangles(tris64, n_tris, aee);
     hrt_lbvh::HostTree T;
-    if (!hrt_lbvh::host_refit(aee_t.data(), aee.data(), n_tris, T))
+    if (!hrt_lbvh::host_refit(aee_t.data(), aee.data(), n_tris, T, builder))
         return fail(RT_ERR_ARG, "rt_host_lbvh_refit: a triangle is finite in one array and not in the other");
     const size_t nodes = T.hnodes.size() / 2;
-    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, 0u, 0u, 0u};
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)T.order.size(), T.finite, T.root, T.depth, T.iterations, T.flat, 0u};
     std::copy(i8, i8 + 8, info);
     for (int k = 0; k < 3; k++) root[k] = T.rc[k];
     root[3] = T.radius;
@@ -1690,6 +1731,22 @@ int rt_get_tri_tree_cost(rt_renderer* r, uint64_t cost[4]) {
     return RT_OK;
 }
 
+// What the renderer walks, in numbers (include/hrt.h). A host SAH tree not built yet is built first.
+int rt_get_tri_tree_info(rt_renderer* r, uint32_t info[8]) {
+    if (!r || !info) return fail(RT_ERR_ARG, "rt_get_tri_tree_info: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_get_tri_tree_info: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_get_tri_tree_info: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    if (int rc = upload_tri_tree(r)) return rc;
+    const bool dev = r->dev_geom;
+    const uint32_t i8[8] = {dev ? r->tb_builder : RT_TREE_HOST_SAH, r->tb_n_nodes, r->tb_n_order, r->tri_tree.root_word,
+                            r->tri_tree.depth, dev ? r->tb_iterations : 0u, dev ? r->tb_flat : 0u, 0u};
+    std::copy(i8, i8 + 8, info);
+    return RT_OK;
+}
+
 int rt_testing_get_tri_tree(rt_renderer* r, void* hnodes_out, size_t hnode_cap, uint32_t* order_out, size_t order_cap,
                             uint32_t info[8], float root[4]) {
     if (!r || !info || !root) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: null");
@@ -1699,7 +1756,9 @@ int rt_testing_get_tri_tree(rt_renderer* r, void* hnodes_out, size_t hnode_cap, 
     if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
     const hrt::TriBvh& T = r->tri_tree;
     const size_t nodes = r->tb_n_nodes, leaves = r->tb_n_order;
-    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)leaves, (uint32_t)leaves, T.root_word, T.depth, 0u, 0u, 0u};
+    const bool dev = r->dev_geom;  // (the two PLOC counts, as rt_host_lbvh_build_with reports them)
+    const uint32_t i8[8] = {(uint32_t)nodes, (uint32_t)leaves, (uint32_t)leaves, T.root_word, T.depth, dev ? r->tb_iterations : 0u,
+                            dev ? r->tb_flat : 0u, 0u};
     std::copy(i8, i8 + 8, info);
     for (int k = 0; k < 3; k++) root[k] = T.root_center[k];
     root[3] = T.root_radius;

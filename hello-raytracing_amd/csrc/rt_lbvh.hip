@@ -7,6 +7,7 @@
 //   k_lbvh_keys      the Morton keys in the root box
 //   (hrt_launch_regroup, mode 2: the stable sort of the keys; rt_regroup.hip)
 //   k_lbvh_topology  Karras' node per lane: parent links, and the child words of the nodes the walk reads
+//                    (builder RT_TREE_PLOC runs rt_ploc.hip's kernels in its place, between the same sort and fit)
 //   k_lbvh_fit       the boxes, bottom up, packed
 // The finite count m' is read on the device; every kernel is launched for the caller's n.
 // Below them: rt_refit_triangles_device's two kernels (k_lbvh_refit_prep, k_lbvh_refit_fit: new boxes on the live tree's
@@ -192,7 +193,9 @@ __global__ __launch_bounds__(256) void k_lbvh_fit(const Launch a) {
 }
 
 // Host-side launcher: the staging and scratch buffers are the renderer's (rt_lbvh.hpp Launch has the sizes). n > 0.
-hipError_t hrt_launch_lbvh(const Launch& a, hipStream_t stream) {
+// In three parts, because the PLOC builder (rt_ploc.hip) runs the first and the last around a topology of its own.
+// Everything up to the sort: the zeroing, the prep, the keys, the stable sort.
+hipError_t hrt_launch_lbvh_front(const Launch& a, hipStream_t stream) {
     const uint32_t n = a.n;
     if (n == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(a.stat, 0, hrt_lbvh::STAT_WORDS * sizeof(uint64_t), stream);
@@ -210,11 +213,24 @@ hipError_t hrt_launch_lbvh(const Launch& a, hipStream_t stream) {
     s.mode = RT_REGROUP_KEYS;
     s.entries = a.sort_entries;
     s.counts = a.sort_counts;
-    e = hrt_launch_regroup(s, n, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lbvh_topology, grid, block, 0, stream, a);
-    hipLaunchKernelGGL(k_lbvh_fit, grid, block, 0, stream, a);
+    return hrt_launch_regroup(s, n, stream);
+}
+
+// The fit over whatever topology the parent links and child words hold.
+hipError_t hrt_launch_lbvh_fit(const Launch& a, hipStream_t stream) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lbvh_fit, dim3((a.n + LBVH_WG - 1u) / LBVH_WG), dim3(LBVH_WG), 0, stream, a);
     return hipGetLastError();
+}
+
+// Builder 0: Karras' topology between the two.
+hipError_t hrt_launch_lbvh(const Launch& a, hipStream_t stream) {
+    const uint32_t n = a.n;
+    if (n == 0) return hipSuccess;
+    const hipError_t e = hrt_launch_lbvh_front(a, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lbvh_topology, dim3((n + LBVH_WG - 1u) / LBVH_WG), dim3(LBVH_WG), 0, stream, a);
+    return hrt_launch_lbvh_fit(a, stream);
 }
 
 // ---- rt_refit_triangles_device: the boxes of a moved mesh on the live tree's topology ----

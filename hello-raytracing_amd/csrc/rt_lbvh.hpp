@@ -23,6 +23,10 @@
 //   refit     (rt_refit_triangles_device, rt_host_lbvh_refit) prep and fit over another array of the same triangles, on
 //             the topology as it stands: the same set of finite triangles is asked for, nothing else.
 //   cost      (rt_get_tri_tree_cost, rt_host_lbvh_cost) cost_node: integers from the packed boxes alone.
+//   ploc      (builder RT_TREE_PLOC: rt_set_triangles_device_with, rt_host_lbvh_build_with; kernels in rt_ploc.hip) a second
+//             topology over the same sorted order: locally-ordered clustering (Meister and Bittner 2018), stated at "the
+//             PLOC topology" below as a pure function. It writes what Karras' construction writes (order, parent links,
+//             child words, node 0 the root), so the fit, the refit, the cost and the walk are the ones above.
 #pragma once
 #include <stdint.h>
 
@@ -270,10 +274,68 @@ HRT_LBVH_FN void cost_node(const U4& l, const U4& r, double R, uint64_t cost[4])
     }
 }
 
+// ---- the PLOC topology (builder 1) ----
+// Clusters: an f64 box and a child word each, at first one per sorted position p (tri_bounds of triangle order[p],
+// LEAF_BIT | p << 4 | 1: every leaf holds one triangle). Iteration t = 0, 1, ... over the list of c >= 2 clusters:
+//   distance   d(i, j) = cost_half_area of the union box's extents (each operation rounded in f64; bitwise symmetric: the
+//              boxes hold no NaN and no -0). Flat mode: when t + clog2(c) >= PLOC_LEVELS, d = 0 for every pair.
+//   neighbour  nn(i) = the j in [i - PLOC_RADIUS, i + PLOC_RADIUS] inside the list, j != i, with the smallest
+//              (d(i, j), i ^ j): a symmetric key, strict among the pairs that share an endpoint, so a mutual pair exists.
+//   merge      i < j merge when nn(i) = j and nn(j) = i. With k such pairs and `next` node ids not given out yet (m' - 1
+//              at first), the s-th pair in order of i becomes node next - k + s, then next -= k: the last merge is node 0
+//              and a child's id is above its parent's. Left word = cluster i's, right word = cluster j's; the merged
+//              cluster (union box, word = id) takes i's place, j is dropped, the others keep their order.
+// A flat iteration leaves ceil(c / 2) clusters, so there are at most PLOC_LEVELS iterations, and a node made in iteration t
+// has height <= t + 1: no leaf has more than 64 nodes above it, the level cap of the fit kernels.
+constexpr int PLOC_RADIUS = 8;
+constexpr uint32_t PLOC_LEVELS = 64;
+constexpr uint32_t PLOC_TAIL = 1024;  // (device) a list this short is finished by one workgroup in one launch
+struct Cluster {                      // 56 B: two lists of n fit in the fit's box slots (BOX_WORDS u64 per side)
+    double lo[3], hi[3];
+    uint32_t word, unused;
+};
+HRT_LBVH_FN uint32_t ploc_clog2(uint32_t c) { return c <= 1u ? 0u : 32u - (uint32_t)clz32(c - 1u); }
+HRT_LBVH_FN bool ploc_flat(uint32_t t, uint32_t c) { return t + ploc_clog2(c) >= PLOC_LEVELS; }
+HRT_LBVH_FN double ploc_distance(const double alo[3], const double ahi[3], const double blo[3], const double bhi[3]) {
+    double e[3];
+    for (int k = 0; k < 3; k++) e[k] = dmax(ahi[k], bhi[k]) - dmin(alo[k], blo[k]);
+    return cost_half_area(e[0], e[1], e[2]);
+}
+// nn(i) in a list of c >= 2 clusters; box(j, lo, hi) gives cluster j's box.
+template <class BoxOf>
+HRT_LBVH_FN int ploc_nearest(const BoxOf& box, int i, int c, bool flat) {
+    double lo[3], hi[3];
+    box(i, lo, hi);
+    const int j0 = i - PLOC_RADIUS < 0 ? 0 : i - PLOC_RADIUS, j1 = i + PLOC_RADIUS > c - 1 ? c - 1 : i + PLOC_RADIUS;
+    int best = -1;
+    double bd = 0.0;
+    for (int j = j0; j <= j1; j++) {
+        if (j == i) continue;
+        double d = 0.0;
+        if (!flat) {
+            double olo[3], ohi[3];
+            box(j, olo, ohi);
+            d = ploc_distance(lo, hi, olo, ohi);
+        }
+        if (best < 0 || d < bd || (d == bd && (i ^ j) < (i ^ best))) {
+            best = j;
+            bd = d;
+        }
+    }
+    return best;
+}
+// The link slot of the cluster with child word `word`: a node's own index, a leaf's position after `leaf_base` (m' on the
+// host, n on the device: HostTopology::parent, Launch::parent).
+HRT_LBVH_FN uint32_t ploc_link_slot(uint32_t word, uint32_t leaf_base) {
+    return (word & LEAF_BIT) != 0u ? leaf_base + ((word & ~LEAF_BIT) >> 4) : word;
+}
+
 // ---- the device build's memory (rt_lbvh.hip; renderer.cpp allocates) ----
 constexpr uint32_t STAT_WORDS = 16;  // u64 each: [0..2] ~f64_key of the root minima, [3..5] f64_key of the root maxima,
                                      // [6] finite triangles, [7] triangles with a bad material index, [8] depth,
                                      // [9] (refit) triangles whose finiteness is not the live tree's,
+                                     // [10] (PLOC) clusters left after an iteration; iterations run, once the tail is done,
+                                     // [11] (PLOC) pairs merged by an iteration; flat iterations, once the tail is done,
                                      // [12..15] (rt_get_tri_tree_cost) the four cost words
 constexpr uint32_t BOX_WORDS = 8;    // u64 per (node, side): lo xyz, hi xyz as f64 bits, the subtree's height, unused
 struct Launch {
@@ -313,6 +375,7 @@ struct HostTree {
     std::vector<U4> hnodes;       // 2 per node slot
     std::vector<uint32_t> order;  // the finite triangles' indices in key order
     uint32_t root = LEAF_BIT, depth = 0, finite = 0;
+    uint32_t iterations = 0, flat = 0;  // (PLOC) of the topology
     float rc[3] = {0, 0, 0};
     float radius = 0;
 };
@@ -328,21 +391,24 @@ inline void root_sphere(const double lo[3], const double hi[3], float rc[3], flo
     *radius = f32_outward(std::sqrt(diag2) * (1.0 + 1e-6), true);
 }
 
-// The build in two halves, so that the refit (rt_host_lbvh_refit) shares them: host_topology is everything that depends on
-// the keys (which triangles are in the tree, their order, the parent links, the child words), host_fit everything that
-// depends on positions alone (the root sphere, the packed boxes, the depth).
+// The build in two halves, so that the refit (rt_host_lbvh_refit) shares them: host_topology (builder 0) or
+// host_topology_ploc (builder 1) is everything that depends on the keys (which triangles are in the tree, their order, the
+// parent links, the child words), host_fit everything that depends on positions alone (the root sphere, the packed boxes,
+// the depth) and nothing on how the topology was made.
 struct HostTopology {
     std::vector<uint8_t> fin;     // per triangle: in the tree
     std::vector<uint32_t> order;  // the finite triangles' indices in key order
     std::vector<uint32_t> parent; // 2 m: of internal node i at [i], of sorted position p at [m + p]: node << 1 | side
     std::vector<U4> words;        // 2 per node slot: only the child words (w) of the referenced nodes are set
     uint32_t finite = 0;
+    uint32_t iterations = 0, flat = 0;  // (PLOC) iterations run, and how many of them in flat mode
 };
 
-// aee: 9 floats per triangle (a, e1, e2), as rt_set_bvh and the prep kernel make them.
-inline HostTopology host_topology(const float* aee, uint32_t n) {
+// Everything up to the sort, which the builders share: the finite set, the keys in the root box, the stable order.
+// aee: 9 floats per triangle (a, e1, e2), as rt_set_bvh and the prep kernel make them. keys: per triangle.
+inline HostTopology host_sorted(const float* aee, uint32_t n, std::vector<uint32_t>& keys) {
     HostTopology P;
-    std::vector<uint32_t> keys(n, KEY_NONFINITE);
+    keys.assign(n, KEY_NONFINITE);
     P.fin.assign(n, 0);
     double rlo[3] = {INFINITY, INFINITY, INFINITY}, rhi[3] = {-INFINITY, -INFINITY, -INFINITY};
     std::vector<double> cen(3 * (size_t)n);
@@ -371,6 +437,14 @@ inline HostTopology host_topology(const float* aee, uint32_t n) {
         idx.swap(tmp);
     }
     P.order.assign(idx.begin(), idx.begin() + m);
+    return P;
+}
+
+// Builder 0: Karras' topology.
+inline HostTopology host_topology(const float* aee, uint32_t n) {
+    std::vector<uint32_t> keys;
+    HostTopology P = host_sorted(aee, n, keys);
+    const uint32_t m = P.finite;
     if (m <= LEAF_MAX) return P;
     std::vector<uint32_t> ks(m);
     for (uint32_t p = 0; p < m; p++) ks[p] = keys[P.order[p]];
@@ -390,6 +464,69 @@ inline HostTopology host_topology(const float* aee, uint32_t n) {
         }
     }
     return P;
+}
+
+// Builder 1: the PLOC topology (the rules above), one iteration after the other. All m' - 1 slots end up referenced.
+inline HostTopology host_topology_ploc(const float* aee, uint32_t n) {
+    std::vector<uint32_t> keys;
+    HostTopology P = host_sorted(aee, n, keys);
+    const uint32_t m = P.finite;
+    if (m <= LEAF_MAX) return P;
+    P.words.assign(2 * (size_t)(m - 1u), U4{0u, 0u, 0u, 0u});
+    P.parent.assign(2 * (size_t)m, NO_PARENT);
+    std::vector<Cluster> cur(m), nxt;
+    for (uint32_t p = 0; p < m; p++) {
+        double cen[3];
+        tri_bounds(aee + 9 * (size_t)P.order[p], cur[p].lo, cur[p].hi, cen);  // (true: a finite one)
+        cur[p].word = LEAF_BIT | p << 4 | 1u;
+        cur[p].unused = 0u;
+    }
+    std::vector<int> nn;
+    uint32_t next = m - 1u;
+    while (cur.size() >= 2) {
+        const int c = (int)cur.size();
+        const bool flat = ploc_flat(P.iterations, (uint32_t)c);
+        const auto box = [&](int j, double lo[3], double hi[3]) {
+            for (int k = 0; k < 3; k++) {
+                lo[k] = cur[(size_t)j].lo[k];
+                hi[k] = cur[(size_t)j].hi[k];
+            }
+        };
+        nn.resize((size_t)c);
+        uint32_t pairs = 0;
+        for (int i = 0; i < c; i++) nn[(size_t)i] = ploc_nearest(box, i, c, flat);
+        for (int i = 0; i < c; i++) pairs += nn[(size_t)i] > i && nn[(size_t)nn[(size_t)i]] == i;
+        uint32_t id = next - pairs;
+        next -= pairs;
+        nxt.clear();
+        for (int i = 0; i < c; i++) {
+            const int j = nn[(size_t)i];
+            const bool mutual = nn[(size_t)j] == i;
+            if (mutual && j < i) continue;  // the higher partner: dropped
+            Cluster a = cur[(size_t)i];
+            if (mutual) {
+                const Cluster& b = cur[(size_t)j];
+                P.words[2 * (size_t)id].w = a.word;
+                P.words[2 * (size_t)id + 1].w = b.word;
+                P.parent[ploc_link_slot(a.word, m)] = id << 1;
+                P.parent[ploc_link_slot(b.word, m)] = id << 1 | 1u;
+                for (int k = 0; k < 3; k++) {
+                    a.lo[k] = dmin(a.lo[k], b.lo[k]);
+                    a.hi[k] = dmax(a.hi[k], b.hi[k]);
+                }
+                a.word = id++;
+            }
+            nxt.push_back(a);
+        }
+        cur.swap(nxt);
+        P.iterations++;
+        P.flat += flat ? 1u : 0u;
+    }
+    return P;
+}
+
+inline HostTopology host_topology_of(const float* aee, uint32_t n, uint32_t builder) {
+    return builder == 1u ? host_topology_ploc(aee, n) : host_topology(aee, n);
 }
 
 // The boxes of `aee` on the topology P (of the same n triangles). False, with T untouched past its defaults, when a
@@ -413,6 +550,8 @@ inline bool host_fit(const HostTopology& P, const float* aee, uint32_t n, HostTr
     const uint32_t m = P.finite;
     T.finite = m;
     T.root = root_word(m);
+    T.iterations = P.iterations;
+    T.flat = P.flat;
     if (m == 0) return true;
     root_sphere(rlo, rhi, T.rc, &T.radius);
     T.order = P.order;
@@ -453,15 +592,16 @@ inline bool host_fit(const HostTopology& P, const float* aee, uint32_t n, HostTr
     return true;
 }
 
-inline HostTree host_build(const float* aee, uint32_t n) {
+// builder: RT_TREE_LBVH (0) or RT_TREE_PLOC (1) of include/hrt.h.
+inline HostTree host_build(const float* aee, uint32_t n, uint32_t builder = 0u) {
     HostTree T;
-    host_fit(host_topology(aee, n), aee, n, T);  // (never false: the same array)
+    host_fit(host_topology_of(aee, n, builder), aee, n, T);  // (never false: the same array)
     return T;
 }
 
 // Topology of aee_topology, boxes of aee (rt_host_lbvh_refit). False for a finiteness mismatch.
-inline bool host_refit(const float* aee_topology, const float* aee, uint32_t n, HostTree& T) {
-    return host_fit(host_topology(aee_topology, n), aee, n, T);
+inline bool host_refit(const float* aee_topology, const float* aee, uint32_t n, HostTree& T, uint32_t builder = 0u) {
+    return host_fit(host_topology_of(aee_topology, n, builder), aee, n, T);
 }
 
 // The cost read-out on the host: every node slot, in any order (the sums are of integers).

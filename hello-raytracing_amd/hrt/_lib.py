@@ -168,6 +168,10 @@ SIGNATURES = {
     "rt_host_lbvh_refit": (C.c_int, [_P, _P, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
     "rt_host_lbvh_cost": (C.c_int, [_P, C.c_size_t, _U32, C.POINTER(C.c_uint64)]),
     "rt_get_tri_tree_cost": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "rt_set_triangles_device_with": (C.c_int, [_P, _P, _U32, _P, _U32, _U32]),
+    "rt_host_lbvh_build_with": (C.c_int, [_P, _U32, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
+    "rt_host_lbvh_refit_with": (C.c_int, [_P, _P, _U32, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
+    "rt_get_tri_tree_info": (C.c_int, [_P, _PU32]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),

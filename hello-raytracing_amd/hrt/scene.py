@@ -342,16 +342,18 @@ class Renderer:
         check(lib().rt_set_bvh(self._h, sz, nodes.ctypes.data, len(nodes), triangles.ctypes.data, len(triangles),
                                materials.ctypes.data, len(materials)), "write_buffer(bvh)")
 
-    def set_triangles_device(self, tris, materials: np.ndarray) -> None:
-        """rt_set_triangles_device: triangles from a contiguous torch tensor on the renderer's device, (m, 16) float32 or
-        (m, 64) uint8 in the layout of TRIANGLE_DTYPE, with an LBVH built for them on the GPU; materials as in write_bvh
-        (numpy). The renderer then has device geometry: every draw and query walks that tree (include/hrt.h).
-        Synchronises torch's current stream before the call; the call itself is synchronous."""
+    def set_triangles_device(self, tris, materials: np.ndarray, builder: int = 0) -> None:
+        """rt_set_triangles_device_with: triangles from a contiguous torch tensor on the renderer's device, (m, 16) float32
+        or (m, 64) uint8 in the layout of TRIANGLE_DTYPE, with a tree built for them on the GPU; materials as in write_bvh
+        (numpy). builder: 0 (RT_TREE_LBVH, the default: the fast Morton-order build) or 1 (RT_TREE_PLOC: a slower build of
+        a tree that is cheaper to walk). The renderer then has device geometry: every draw and query walks that tree
+        (include/hrt.h). Synchronises torch's current stream before the call; the call itself is synchronous."""
         stream = self._check_device_triangles(tris, "set_triangles_device")
         materials = np.ascontiguousarray(materials, dtype=MATERIAL_DTYPE)
         stream.synchronize()
-        check(lib().rt_set_triangles_device(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0]),
-                                            materials.ctypes.data, len(materials)), "set_triangles_device")
+        check(lib().rt_set_triangles_device_with(self._h, C.c_void_p(tris.data_ptr()), int(tris.shape[0]),
+                                                 materials.ctypes.data, len(materials), _builder(builder)),
+              "set_triangles_device")
 
     def _check_device_triangles(self, tris, where: str):
         """The tensor checks of set_triangles_device / refit_triangles_device; returns torch's current stream on the
@@ -388,6 +390,14 @@ class Renderer:
         cost = (C.c_uint64 * 4)()
         check(lib().rt_get_tri_tree_cost(self._h, cost), "tri_tree_cost")
         return np.array(list(cost), dtype=np.uint64)
+
+    def tri_tree_info(self) -> np.ndarray:
+        """rt_get_tri_tree_info: eight uint32 of the triangle tree the renderer walks: builder (0 LBVH, 1 PLOC,
+        0xFFFFFFFF the host SAH tree of tri_bvh = 1), node slots, finite triangles, root word, depth, PLOC iterations,
+        flat ones among them, 0. RtError without a triangle tree."""
+        info = (C.c_uint32 * 8)()
+        check(lib().rt_get_tri_tree_info(self._h, info), "tri_tree_info")
+        return np.array(list(info), dtype=np.uint32)
 
     def tri_tree(self) -> dict:
         """Test-only (include/hrt_testing.h rt_testing_get_tri_tree): the triangle tree the renderer walks, read back, in
@@ -836,16 +846,25 @@ def _tree_dict(call, where: str) -> dict:
             "root": np.array(list(root), dtype=np.float32)}
 
 
-def lbvh_build(triangles: np.ndarray) -> dict:
-    """rt_host_lbvh_build (include/hrt.h): rt_set_triangles_device's builder on the host, no device. triangles:
-    TRIANGLE_DTYPE records (or (m, 16) float32). Returns nodes (slots, 8) uint32 — per child [min | max << 16] fp16 bounds
-    per axis relative to the root centre, then the child word —, order (the finite triangles' indices in key order), info
-    {node slots, leaf positions, finite triangles, root word, depth, 0, 0, 0} and root (centre xyz, radius)."""
+def _builder(builder) -> int:
+    """A builder argument as the uint32 the library takes (which refuses the unknown ones)."""
+    b = int(builder)
+    if not 0 <= b <= 0xFFFFFFFF:
+        raise ValueError(f"builder must be 0 (LBVH) or 1 (PLOC), got {builder!r}")
+    return b
+
+
+def lbvh_build(triangles: np.ndarray, builder: int = 0) -> dict:
+    """rt_host_lbvh_build_with (include/hrt.h): rt_set_triangles_device's builders on the host, no device. triangles:
+    TRIANGLE_DTYPE records (or (m, 16) float32); builder: 0 (LBVH) or 1 (PLOC). Returns nodes (slots, 8) uint32 — per
+    child [min | max << 16] fp16 bounds per axis relative to the root centre, then the child word —, order (the finite
+    triangles' indices in key order), info {node slots, leaf positions, finite triangles, root word, depth, PLOC's
+    iterations, the flat ones among them, 0} and root (centre xyz, radius)."""
     t = np.ascontiguousarray(triangles)
     if t.dtype != TRIANGLE_DTYPE:
         t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 16)
-    m, p = len(t), t.ctypes.data
-    return _tree_dict(lambda *a: lib().rt_host_lbvh_build(p if m else None, m, *a), "rt_host_lbvh_build")
+    m, p, b = len(t), t.ctypes.data, _builder(builder)
+    return _tree_dict(lambda *a: lib().rt_host_lbvh_build_with(p if m else None, m, b, *a), "rt_host_lbvh_build")
 
 
 def _triangle_records(triangles: np.ndarray) -> np.ndarray:
@@ -855,15 +874,16 @@ def _triangle_records(triangles: np.ndarray) -> np.ndarray:
     return t
 
 
-def lbvh_refit(topology_triangles: np.ndarray, triangles: np.ndarray) -> dict:
-    """rt_host_lbvh_refit (include/hrt.h): rt_refit_triangles_device on the host, no device. The tree has the topology
-    lbvh_build gives topology_triangles and the boxes of triangles (the same count; a triangle finite in one array and
-    not in the other is an RtError). The dict is lbvh_build's."""
+def lbvh_refit(topology_triangles: np.ndarray, triangles: np.ndarray, builder: int = 0) -> dict:
+    """rt_host_lbvh_refit_with (include/hrt.h): rt_refit_triangles_device on the host, no device. The tree has the
+    topology lbvh_build(topology_triangles, builder) has and the boxes of triangles (the same count; a triangle finite in
+    one array and not in the other is an RtError). The dict is lbvh_build's."""
     a, b = _triangle_records(topology_triangles), _triangle_records(triangles)
     if len(a) != len(b):
         raise ValueError(f"lbvh_refit: {len(a)} triangles for the topology, {len(b)} to fit")
-    m, pa, pb = len(a), a.ctypes.data, b.ctypes.data
-    return _tree_dict(lambda *x: lib().rt_host_lbvh_refit(pa if m else None, pb if m else None, m, *x), "rt_host_lbvh_refit")
+    m, pa, pb, bld = len(a), a.ctypes.data, b.ctypes.data, _builder(builder)
+    return _tree_dict(lambda *x: lib().rt_host_lbvh_refit_with(pa if m else None, pb if m else None, m, bld, *x),
+                      "rt_host_lbvh_refit")
 
 
 def lbvh_cost(tree: dict) -> np.ndarray:

@@ -229,6 +229,27 @@ int rt_set_bvh(rt_renderer *r, const uint32_t sizes[2], const void *nodes32, uin
  * The image, the frame count and rt_get_stats are not touched; the learnt cost order is dropped, as by rt_set_bvh. */
 int rt_set_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_tris, const void *mats32,
                             uint32_t n_mats);
+/* The same call with the topology builder named. RT_TREE_LBVH is rt_set_triangles_device exactly (which is this call with
+ * it). RT_TREE_PLOC keeps everything up to the sort and everything after the topology (the fit, the packing, the root
+ * sphere, the refit, the cost read-out, the walk) and replaces Karras' construction by parallel locally-ordered clustering
+ * (Meister and Bittner 2018) over the sorted order; csrc/rt_lbvh.hpp states it as a pure function, DESIGN.md §7d has the
+ * reasons and the measurements. In words: one cluster per sorted position p (the triangle's f64 box, the leaf word
+ * 0x80000000 | p << 4 | 1: every leaf holds ONE triangle); per iteration every cluster i finds, among the up to 8 clusters
+ * on each side, the j with the smallest (half-area of the union box, i XOR j), and i, j merge when each is the other's
+ * choice; the s-th of an iteration's k pairs, in list order, becomes node next - k + s (next: the ids not given out, m' - 1
+ * at first), so node 0 is the root, all m' - 1 slots are referenced and a child's index is above its parent's; the merged
+ * cluster stays in the lower partner's place. An iteration t with t + ceil(log2(clusters)) >= 64 takes every distance as 0
+ * ("flat": clusters 2 s and 2 s + 1 merge), which bounds the build at 64 iterations and the tree at 64 levels. m' <= 4
+ * finite triangles give builder 0's tree (one leaf word, no nodes). The tree is slower to build (it reads a cluster count
+ * back per iteration until 1024 clusters are left) and cheaper to walk; its depth may exceed the walk's stack of 24, which
+ * the walk's overflow path answers correctly and slowly: rt_get_tri_tree_info reports the depth.
+ * RT_ERR_ARG also for an unknown builder; everything else (arguments, staging, failure keeps the geometry, synchronous,
+ * rt_stats.device_bytes, rt_release_scratch) is rt_set_triangles_device's. */
+#define RT_TREE_LBVH 0u
+#define RT_TREE_PLOC 1u
+#define RT_TREE_HOST_SAH 0xFFFFFFFFu /* reported by rt_get_tri_tree_info for the host tree of tri_bvh = 1; not a builder argument */
+int rt_set_triangles_device_with(rt_renderer *r, const void *tris64_dev, uint32_t n_tris, const void *mats32,
+                                 uint32_t n_mats, uint32_t builder);
 /* The same builder on the host, for n_tris Triangle records in host memory: pure CPU, no device, usable without a GPU,
  * and what the tests compare the device tree with. hnodes_out: 32 B per node slot (per child six fp16 box bounds relative
  * to the root centre, [min | max << 16] per axis, then the child word: a node index, or
@@ -238,6 +259,11 @@ int rt_set_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_t
  * always written. With both capacities 0 only they are returned; a capacity that is too small otherwise is RT_ERR_ARG. */
 int rt_host_lbvh_build(const void *tris64, uint32_t n_tris, void *hnodes_out, size_t hnode_cap, uint32_t *order_out,
                        size_t order_cap, uint32_t info[8], float root[4]);
+/* The same with the builder named: RT_TREE_LBVH is rt_host_lbvh_build's bytes; RT_TREE_PLOC is the host mirror of
+ * rt_set_triangles_device_with's tree, with info[5] = iterations run and info[6] = how many of them were flat (both 0
+ * for builder 0 and for a tree without nodes). RT_ERR_ARG for an unknown builder. */
+int rt_host_lbvh_build_with(const void *tris64, uint32_t n_tris, uint32_t builder, void *hnodes_out, size_t hnode_cap,
+                            uint32_t *order_out, size_t order_cap, uint32_t info[8], float root[4]);
 /* Refit: the moved positions of a mesh that keeps its connectivity, on the tree of the last successful
  * rt_set_triangles_device. tris64_dev: the same records as there (64 B each, device memory on the renderer's GPU, 16-byte
  * aligned); n_tris must equal that build's count. Kept: the build's topology, that is the sorted order, the parent links
@@ -260,13 +286,18 @@ int rt_host_lbvh_build(const void *tris64, uint32_t n_tris, void *hnodes_out, si
  * part of the tree (counted in rt_stats.device_bytes, kept by rt_release_scratch, untouched by a build that fails): a
  * refit after rt_release_scratch allocates staging and scratch again, a refit after a failed build uses the live tree.
  * Synchronous on the renderer's stream like the build; drops the learnt cost order; image, frame count and rt_get_stats
- * are not touched. */
+ * are not touched. The refit reads the live topology whichever builder made it: its host mirror is
+ * rt_host_lbvh_refit_with with the builder of the last successful build. */
 int rt_refit_triangles_device(rt_renderer *r, const void *tris64_dev, uint32_t n_tris);
 /* The refit on the host: the topology rt_host_lbvh_build gives tris64_topology, the boxes of tris64 (n_tris records each,
  * host memory). Outputs, capacities and the two-call protocol are rt_host_lbvh_build's. RT_ERR_ARG also when a triangle
  * is finite in one array and not in the other. rt_host_lbvh_refit(A, A) is rt_host_lbvh_build(A). */
 int rt_host_lbvh_refit(const void *tris64_topology, const void *tris64, uint32_t n_tris, void *hnodes_out,
                        size_t hnode_cap, uint32_t *order_out, size_t order_cap, uint32_t info[8], float root[4]);
+/* The same on the topology rt_host_lbvh_build_with(tris64_topology, builder) gives; info as there. */
+int rt_host_lbvh_refit_with(const void *tris64_topology, const void *tris64, uint32_t n_tris, uint32_t builder,
+                            void *hnodes_out, size_t hnode_cap, uint32_t *order_out, size_t order_cap, uint32_t info[8],
+                            float root[4]);
 /* Tree cost: a deterministic read-out of any tree in the node format above (the host SAH tree of tri_bvh = 1 included),
  * in integers, so that no summation order can matter; a pure function of the bytes. A referenced node is a slot whose left
  * child word is not 0. Per child of one: the six halves decoded to f64; per axis e = hi - lo, 0 if !(e > 0), 131008 if
@@ -279,6 +310,12 @@ int rt_host_lbvh_cost(const void *hnodes, size_t node_slots, uint32_t root_word,
 /* The same read-out, by a small kernel, of the tree the renderer walks with tri_bvh = 1 or with device geometry (a host
  * SAH tree not built yet is built first). Blocking. RT_ERR_ARG in the sphere program. Touches nothing a draw reads. */
 int rt_get_tri_tree_cost(rt_renderer *r, uint64_t cost[4]);
+/* The triangle tree the renderer walks, in numbers: {builder, node slots, finite triangles, root word, depth, iterations,
+ * flat iterations, 0}. builder: RT_TREE_LBVH or RT_TREE_PLOC with device geometry, RT_TREE_HOST_SAH for the host tree of
+ * tri_bvh = 1 (built first if it is not yet); the two iteration counts are 0 unless PLOC built nodes. A depth above 24 means
+ * that rays can leave the walk's stack for its slow overflow path. RT_ERR_ARG in the sphere program; RT_ERR_STATE when
+ * there is no triangle tree (no device geometry and tri_bvh = 0). Touches nothing a draw reads. */
+int rt_get_tri_tree_info(rt_renderer *r, uint32_t info[8]);
 
 /* Renderer::set_time / set_frame_count — renderer.rs:315-323. */
 int rt_set_time(rt_renderer *r, uint32_t time);
@@ -568,7 +605,9 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
                              5: rt_params.cost_order, rt_stats.ordered_launches. rt_cast_rays / rt_primary_rays / rt_get_stream, then
                              rt_occluded, then rt_trace_rays / rt_primary_rng, then rt_bounce_rays, then rt_regroup_paths /
                              rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, then
-                             rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, came
+                             rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, then
+                             rt_set_triangles_device_with / rt_host_lbvh_build_with / rt_host_lbvh_refit_with /
+                             rt_get_tri_tree_info, came
                              later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 

@@ -69,7 +69,8 @@ int rt_testing_sphere_bvh_leaves(const float *centers_radii, uint32_t n_slots, u
                                  int32_t *slots, uint32_t slot_cap, uint32_t counts[4]);
 
 /* Blocking read-back of the triangle tree the renderer walks with tri_bvh = 1 or with device geometry, in the format
- *   and with the capacity rules of rt_host_lbvh_build (info[1] = info[2] = the leaf positions). A host SAH tree that
+ *   and with the capacity rules of rt_host_lbvh_build_with (info[1] = info[2] = the leaf positions; info[5], [6] the
+ *   PLOC iteration counts of device geometry built with RT_TREE_PLOC, else 0). A host SAH tree that
  *   was not built yet (rt_set_bvh, no tri_bvh = 1 query so far) is built first. RT_ERR_ARG in the sphere program. */
 int rt_testing_get_tri_tree(rt_renderer *r, void *hnodes_out, size_t hnode_cap, uint32_t *order_out, size_t order_cap,
                             uint32_t info[8], float root[4]);

@@ -22,6 +22,7 @@
 #include "host/sphere_bvh.hpp"
 #include "host/tri_bvh.hpp"
 #include "rt_device.hpp"
+#include "rt_closest.hpp"
 #include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
 #include "rt_tile_lists.hpp"
@@ -44,6 +45,7 @@ hipError_t hrt_launch_lbvh(const hrt_lbvh::Launch& a, hipStream_t stream);      
 hipError_t hrt_launch_lbvh_refit(const hrt_lbvh::Refit& a, hipStream_t stream);                // rt_lbvh.hip
 hipError_t hrt_launch_lbvh_ploc(const hrt_lbvh::Launch& a, uint64_t* pinned, hipStream_t stream);  // rt_ploc.hip
 hipError_t hrt_launch_tri_tree_cost(const void* hnodes, uint32_t slots, uint32_t root, uint64_t* out, hipStream_t stream);  // rt_lbvh.hip
+hipError_t hrt_launch_closest(const hrt_closest::Launch& a, bool count, hipStream_t stream);      // rt_closest.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -258,6 +260,9 @@ struct rt_renderer {
     size_t wave_trace_words = 0;
     // rt_regroup_paths' sort: 4 u32 per entry, and the digit counts (rt_regroup.hpp Launch; include/hrt.h has the size rule)
     DevBuf<uint32_t> regroup_entries, regroup_counts;
+    // rt_closest_points' counting instantiation (hrt_testing.h): selected by closest_count, its four words
+    DevBuf<unsigned long long> closest_counts;
+    bool closest_count = false;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -287,7 +292,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -1182,6 +1187,7 @@ void delete_buffers(rt_renderer* r) {
     r->tile_sum.release();
     r->tile_order.release();
     r->tile_lists.release();
+    r->closest_counts.release();
     r->tile_lists_valid = false;
     r->order_scratch.release();
     r->cost_tiles = r->order_tiles = 0;
@@ -2040,6 +2046,77 @@ int rt_bounce_rays(rt_renderer* r, const rt_bounce* io, uint32_t n) {
 
 // Regrouping (include/hrt.h rt_regroup): the key pass and the radix sort of rt_regroup.hip in the renderer's own scratch.
 // No scene, camera or draw state is read.
+// The point query (include/hrt.h; rt_closest.hip k_closest_points, rt_closest.hpp the function and the definition). Like
+// the ray queries it reads the scene through scene_params and nothing of a draw's state.
+int rt_closest_points(rt_renderer* r, const void* points_dev, const void* maxd2_dev, uint32_t n, void* out_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_closest_points: null");
+    if (n == 0) return RT_OK;
+    if (!points_dev || !out_dev) return fail(RT_ERR_ARG, "rt_closest_points: null buffer");
+    if (misaligned(16, {out_dev}) || misaligned(4, {points_dev, maxd2_dev}))
+        return fail(RT_ERR_ARG, "rt_closest_points: out must be 16-byte aligned, points and maxd2 4-byte aligned");
+    static_assert(sizeof(rt_closest) == 32, "rt_closest: two 16-byte stores per record (k_closest_points)");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_closest_points: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_closest_points: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    if (q.rc) return q.rc;
+    hrt_closest::Launch a{};
+    a.hnodes = (const hrt_closest::U4*)q.P.tb_hnodes;
+    a.order = q.P.tb_order;
+    a.geo = q.P.tri_geo;
+    a.m = q.P.m;
+    a.root = q.P.tb_root;
+    for (int k = 0; k < 3; k++) a.rc[k] = q.P.tb_rc[k];
+    a.rr_h = q.P.tb_rr_h;
+    a.points = (const float*)points_dev;
+    a.maxd2 = (const float*)maxd2_dev;
+    a.out = out_dev;
+    a.n = n;
+    if (r->closest_count) {
+        if (int rc = ensure(r->closest_counts, 4)) return rc;
+        HIP_TRY(hipMemsetAsync(r->closest_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
+        a.counts = r->closest_counts.ptr;
+    }
+    HIP_TRY(hrt_launch_closest(a, r->closest_count, r->stream));
+    return RT_OK;
+}
+
+// The definition on the host (rt_closest.hpp host_closest): pure CPU, no device.
+int rt_host_closest_points(const void* tris64, uint32_t n_tris, const float* points, const float* maxd2, uint32_t n,
+                           void* out32) {
+    if (n_tris && !tris64) return fail(RT_ERR_ARG, "rt_host_closest_points: null triangles");
+    if (n && (!points || !out32)) return fail(RT_ERR_ARG, "rt_host_closest_points: null points or out");
+    std::vector<float> aee(9 * (size_t)n_tris);
+    for (uint32_t j = 0; j < n_tris; j++) {
+        hrt::Triangle t;  // (no alignment asked of the caller)
+        std::memcpy(&t, (const char*)tris64 + 64u * (size_t)j, sizeof t);
+        const float v[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z,
+                            t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
+        std::copy(v, v + 9, &aee[9 * (size_t)j]);
+    }
+    std::vector<hrt_closest::Record> out(n);
+    hrt_closest::host_closest(aee.data(), n_tris, points, maxd2, n, out.data());
+    if (n) std::memcpy(out32, out.data(), (size_t)n * sizeof(hrt_closest::Record));
+    return RT_OK;
+}
+
+int rt_testing_set_closest_count(rt_renderer* r, uint32_t on) {
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_closest_count: null");
+    r->closest_count = on != 0u;
+    return RT_OK;
+}
+
+int rt_testing_get_closest_counts(rt_renderer* r, uint64_t out[4]) {
+    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_closest_counts: null");
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    if (!r->closest_counts.ptr) return RT_OK;
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    HIP_TRY(hipMemcpyAsync(out, r->closest_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
 int rt_regroup_paths(rt_renderer* r, const rt_regroup* io, uint32_t n) {
     if (!r) return fail(RT_ERR_ARG, "rt_regroup_paths: null");
     if (n == 0) return RT_OK;

@@ -172,6 +172,8 @@ SIGNATURES = {
     "rt_host_lbvh_build_with": (C.c_int, [_P, _U32, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
     "rt_host_lbvh_refit_with": (C.c_int, [_P, _P, _U32, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
     "rt_get_tri_tree_info": (C.c_int, [_P, _PU32]),
+    "rt_closest_points": (C.c_int, [_P, _P, _P, _U32, _P]),
+    "rt_host_closest_points": (C.c_int, [_P, _U32, _PF, _PF, _U32, _P]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),
@@ -227,6 +229,8 @@ TESTING_SIGNATURES = {
     "rt_testing_sphere_bvh_leaves": (C.c_int, [C.POINTER(C.c_float), _U32, C.POINTER(_U32), _U32,
                                                C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
     "rt_testing_get_tri_tree": (C.c_int, [_P, _P, C.c_size_t, _PU32, C.c_size_t, _PU32, _PF]),
+    "rt_testing_set_closest_count": (C.c_int, [_P, _U32]),
+    "rt_testing_get_closest_counts": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -46,6 +46,10 @@ TRIANGLE_DTYPE = np.dtype([("a", "<f4", 4), ("b", "<f4", 4), ("c", "<f4", 4), ("
 HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("n", "<f4", 3), ("flags", "<u4"), ("material", "<u4"),
                       ("reserved", "<u4")])
 assert HIT_DTYPE.itemsize == 32
+# rt_closest (include/hrt.h): one record of rt_closest_points
+CLOSEST_DTYPE = np.dtype([("d2", "<f4"), ("prim", "<i4"), ("p", "<f4", 3), ("v", "<f4"), ("w", "<f4"),
+                          ("reserved", "<u4")])
+assert CLOSEST_DTYPE.itemsize == 32
 assert CAMERA_DTYPE.itemsize == 80 and MATERIAL_DTYPE.itemsize == 32 and SPHERE_DTYPE.itemsize == 48
 assert NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 64
 
@@ -590,6 +594,65 @@ class Renderer:
         self._query("occluded", lib().rt_occluded, _ptr(o), _ptr(d), _ptr(t), n, _ptr(out))
         return out != 0
 
+    def closest_records(self, points, max_dist2=None):
+        """rt_closest_points, the raw records: an (N, 8) int32 tensor on the renderer's device, one 32-byte rt_closest
+        per point (CLOSEST_DTYPE on the host). points: (N, 3) float32, a torch tensor on the renderer's device or a
+        numpy array; max_dist2: None (however far), a Python float for every point, or an (N,) float32 numpy array or
+        tensor on the renderer's device — the squared search radius. Synchronises torch's current stream before the
+        call and the renderer after it."""
+        import torch
+
+        who = "closest_points"
+        pts = self._rays_on_device(who, points, "points")
+        n = int(pts.shape[0])
+        if n >= 1 << 32:
+            raise ValueError(f"{who}: at most 2^32 - 1 points per call")
+        dev = self._torch_device()
+        cap = None
+        if max_dist2 is not None:
+            if isinstance(max_dist2, (int, float)):
+                cap = torch.full((n,), float(max_dist2), dtype=torch.float32, device=dev)
+            else:
+                cap = max_dist2
+                if not torch.is_tensor(cap):
+                    cap = np.asarray(cap)
+                    if cap.dtype != np.float32:
+                        raise ValueError(f"{who}: max_dist2 must be float32, got {cap.dtype}")
+                    cap = torch.from_numpy(np.ascontiguousarray(cap)).to(dev)
+                if cap.dtype != torch.float32 or tuple(cap.shape) != (n,):
+                    raise ValueError(f"{who}: max_dist2 must be ({n},) float32, got {tuple(cap.shape)} {cap.dtype}")
+                if cap.device != dev:
+                    raise ValueError(f"{who}: max_dist2 is on {cap.device}, the renderer draws on {dev}")
+                cap = cap.contiguous()
+        out = torch.empty((n, CLOSEST_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
+        self._query(who, lib().rt_closest_points, _ptr(pts), _ptr(cap), n, _ptr(out))
+        return out
+
+    def closest_points(self, points, max_dist2=None) -> dict:
+        """rt_closest_points: the nearest point of the renderer's triangles for each point (triangle and mixed programs,
+        with device geometry or tri_bvh = 1; the spheres of the mixed program do not answer). Arguments as
+        closest_records. Returns torch tensors on the renderer's device: d2 (N,) float32, the squared distance (RT_T_MISS
+        for a miss: nothing nearer than max_dist2, or a non-finite point), prim (N,) int32 (-1 for a miss), point (N, 3)
+        float32, and v, w (N,) float32, the weights of the triangle's b and c (a's is 1 - v - w)."""
+        import torch
+
+        rec = self.closest_records(points, max_dist2)
+        f = rec.view(torch.float32)
+        return {"d2": f[:, 0].clone(), "prim": rec[:, 1].clone(), "point": f[:, 2:5].clone(), "v": f[:, 5].clone(),
+                "w": f[:, 6].clone()}
+
+    def set_closest_count(self, on: bool) -> None:
+        """Test-only: closest_points runs the counting instantiation of its kernel (include/hrt_testing.h
+        rt_testing_set_closest_count)."""
+        check(lib().rt_testing_set_closest_count(self._h, 1 if on else 0), "testing_set_closest_count")
+
+    def closest_counts(self) -> np.ndarray:
+        """Test-only: uint64[4] of the last counted closest_points call: queries, point-triangle tests, stack overflows,
+        points outside the walk's error bound (include/hrt_testing.h rt_testing_get_closest_counts)."""
+        c = (C.c_uint64 * 4)()
+        check(lib().rt_testing_get_closest_counts(self._h, c), "testing_get_closest_counts")
+        return np.array(list(c), dtype=np.uint64)
+
     def primary_rays(self, time: int):
         """rt_primary_rays: (origins, dirs), each (local_rows, width, 3) float32 on the renderer's device — the rays the
         frame drawn at `time` traces first for each of this renderer's pixels."""
@@ -895,6 +958,26 @@ def lbvh_cost(tree: dict) -> np.ndarray:
     check(lib().rt_host_lbvh_cost(nodes.ctypes.data if len(nodes) else None, len(nodes), int(tree["info"][3]), cost),
           "rt_host_lbvh_cost")
     return np.array(list(cost), dtype=np.uint64)
+
+
+def closest_points_host(triangles: np.ndarray, points: np.ndarray, max_dist2=None) -> np.ndarray:
+    """rt_host_closest_points (include/hrt.h): the definition of Renderer.closest_points as a loop over every triangle, on
+    the host, no device. triangles: TRIANGLE_DTYPE records (or (m, 16) float32); points: (n, 3) float32; max_dist2: None,
+    a float for every point, or (n,) float32. Returns n CLOSEST_DTYPE records: the bytes the device writes."""
+    t = _triangle_records(triangles)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n, m = len(p), len(t)
+    cap = None
+    if max_dist2 is not None:
+        cap = (np.full((n,), max_dist2, dtype=np.float32) if isinstance(max_dist2, (int, float))
+               else np.ascontiguousarray(max_dist2, dtype=np.float32))
+        if cap.shape != (n,):
+            raise ValueError(f"closest_points_host: max_dist2 must be ({n},) float32, got {cap.shape}")
+    out = np.zeros((n,), dtype=CLOSEST_DTYPE)
+    check(lib().rt_host_closest_points(t.ctypes.data if m else None, m, p.ctypes.data_as(_lib._PF) if n else None,
+                                       cap.ctypes.data_as(_lib._PF) if cap is not None and n else None, n,
+                                       out.ctypes.data if n else None), "rt_host_closest_points")
+    return out
 
 
 def render_ppm(renderer: Renderer) -> str:

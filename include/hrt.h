@@ -533,6 +533,52 @@ int rt_primary_rng(rt_renderer *r, uint32_t time, void *rng_dev, size_t n_rays);
  * times them (scripts/bench_cast.py). */
 int rt_get_stream(const rt_renderer *r, void **hip_stream);
 
+/* ---- point queries (no reference counterpart) ----
+ * The nearest point of the triangle set for each of the caller's points, on the triangle tree the ray queries walk: how
+ * far is this point from the surface, and where on it (contact and penetration tests, snapping and projection, chamfer
+ * and point-to-surface losses, attaching particles to a skinned mesh). Unsigned: there is no inside or outside here. */
+typedef struct rt_closest {         /* 32 B */
+    float d2; int32_t prim;         /* squared distance, triangle index; miss: RT_T_MISS, -1, everything below 0 */
+    float p[3];                     /* the closest point: a + (v e1 + w e2) */
+    float v, w;                     /* weights of b and c; a's is 1 - v - w */
+    uint32_t reserved;              /* 0 */
+} rt_closest;
+/* n points -> n rt_closest records. points_dev: n x 3 f32, packed (12-byte stride, 4-byte aligned); maxd2_dev: n f32
+ * (4-byte aligned), the squared search radius of each point, or NULL = RT_T_MISS for every point ("however far");
+ * out_dev: n x 32 B, 16-byte aligned; exactly 32 n bytes are written. All three are device memory on the renderer's GPU.
+ * Asynchronous on the renderer's stream, exactly as rt_cast_rays is.
+ * The answer, stated without a tree. Triangle j is its (a, e1, e2) record: a, e1 = b - a and e2 = c - a, the subtractions
+ * in f32, as rt_set_bvh and rt_set_triangles_device keep it. One function of the point and that record gives (d2_j, v, w):
+ * the nearest of five candidates — the nearest points of the edges ab, ac and bc, each by a clamped segment parameter,
+ * and the projection onto the plane, as solved and after one refinement step, when it falls inside — in f32 with every operation rounded once in a fixed order, no
+ * FMA, IEEE division, starting with p - a (a mesh far from the origin loses nothing); v >= 0, w >= 0 and v + w <= 1 hold
+ * for every input, and d2_j is |(p - a) - (v e1 + w e2)|^2 evaluated for exactly those v, w (csrc/rt_closest.hpp is the
+ * function; DESIGN.md §7e has its properties and its error bound). With cap = maxd2[i], or RT_T_MISS without maxd2,
+ * record i holds the lexicographic minimum (d2_j, j) over the triangles with d2_j < cap, an f32 comparison: the smallest
+ * squared distance, and among equal ones the smallest index; prim = j, v and w that triangle's, and p[k] = a[k] +
+ * (v e1[k] + w e2[k]) rounded in that order. It is a miss when there is no such triangle.
+ *   - A NaN d2_j is never accepted: a triangle with a non-finite a, e1 or e2 never answers, a non-finite point misses, and
+ *     a distance whose square overflows (+inf) is below no cap.
+ *   - A d2_j equal to the cap does not count. A NaN cap, or any cap <= 0 including -0, gives a miss; a cap above RT_T_MISS
+ *     (+inf, FLT_MAX) behaves as RT_T_MISS. These are rt_occluded's tmax rules.
+ *   - A zero-length edge or a zero-area triangle answers as the vertex or the edge it is: no NaN comes from finite input.
+ * rt_host_closest_points is that sentence as a loop over every triangle, and the device returns its bytes: the tree only
+ * skips triangles that cannot be accepted (a small cap skips most of the tree from the first node).
+ * Programs and states: RT_ERR_ARG in the sphere program. The triangle and mixed programs need a triangle tree: device
+ * geometry (rt_set_triangles_device, built or refitted) or rt_params.tri_bvh = 1 (the host SAH tree is built first if it
+ * is not yet, as rt_get_tri_tree_cost does); RT_ERR_STATE without one, as rt_get_tri_tree_info. The spheres of the mixed
+ * program are not part of the query: only triangles answer. A tree deeper than 24 (rt_get_tri_tree_info) can send points
+ * to a slow, correct path, as it does rays.
+ * n = 0 returns RT_OK and launches nothing. RT_ERR_ARG: n > 0 with a null points_dev or out_dev; a misaligned buffer. Like
+ * the ray queries, it touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_closest_points(rt_renderer *r, const void *points_dev, const void *maxd2_dev, uint32_t n, void *out_dev);
+/* The definition on the host: pure CPU, no device. tris64: n_tris Triangle records (64 B each, as rt_set_bvh takes them;
+ * no alignment asked); e1 = b - a and e2 = c - a are formed in f32 as the prep does. points: n x 3 f32; maxd2: n f32 or
+ * NULL; out32: n rt_closest records (no alignment asked). RT_ERR_ARG: a null tris64 with n_tris > 0, or a null points or
+ * out32 with n > 0. */
+int rt_host_closest_points(const void *tris64, uint32_t n_tris, const float *points, const float *maxd2,
+                           uint32_t n, void *out32);
+
 /* Test-only entry points (fault injection) are declared in hrt_testing.h, not here: they are not part of
  * the drop-in surface. */
 
@@ -607,7 +653,7 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
                              rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, then
                              rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, then
                              rt_set_triangles_device_with / rt_host_lbvh_build_with / rt_host_lbvh_refit_with /
-                             rt_get_tri_tree_info, came
+                             rt_get_tri_tree_info, then rt_closest_points / rt_host_closest_points, came
                              later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 

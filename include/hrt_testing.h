@@ -82,6 +82,15 @@ int rt_testing_get_tri_tree(rt_renderer *r, void *hnodes_out, size_t hnode_cap, 
  *   returned; a smaller cap otherwise is RT_ERR_ARG. */
 int rt_testing_get_tile_order(rt_renderer *r, uint32_t *sum_out, uint32_t *order_out, size_t cap, size_t *count);
 
+/* on != 0: rt_closest_points launches the counting instantiation of its kernel (k_closest_points<true>: the same walk
+ *   and the same records, plus four sums per wave added to four words with one agent-scope atomic each); 0: the product
+ *   kernel, which holds no counting code. Stays set until changed; a new renderer starts with 0. */
+int rt_testing_set_closest_count(rt_renderer *r, uint32_t on);
+/* Blocking: the four words of the last rt_closest_points call made with counting on (zeros before the first): {queries,
+ *   point-triangle tests, queries that overflowed the walk's stack and finished with the loop over all triangles, queries
+ *   that took that loop instead of the walk because the walk's error bound does not cover the point}. */
+int rt_testing_get_closest_counts(rt_renderer *r, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 #include "rt_closest.hpp"
 #include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
+#include "rt_winding.hpp"
 #include "rt_tile_lists.hpp"
 
 hipError_t hrt_launch_render(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
@@ -46,6 +47,8 @@ hipError_t hrt_launch_lbvh_refit(const hrt_lbvh::Refit& a, hipStream_t stream); 
 hipError_t hrt_launch_lbvh_ploc(const hrt_lbvh::Launch& a, uint64_t* pinned, hipStream_t stream);  // rt_ploc.hip
 hipError_t hrt_launch_tri_tree_cost(const void* hnodes, uint32_t slots, uint32_t root, uint64_t* out, hipStream_t stream);  // rt_lbvh.hip
 hipError_t hrt_launch_closest(const hrt_closest::Launch& a, bool count, hipStream_t stream);      // rt_closest.hip
+hipError_t hrt_launch_winding(const hrt_winding::Launch& a, bool count, hipStream_t stream);      // rt_winding.hip
+hipError_t hrt_launch_tree_moments(const hrt_winding::MomentsLaunch& a, hipStream_t stream);      // rt_winding.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -263,6 +266,12 @@ struct rt_renderer {
     // rt_closest_points' counting instantiation (hrt_testing.h): selected by closest_count, its four words
     DevBuf<unsigned long long> closest_counts;
     bool closest_count = false;
+    // rt_winding_numbers: the moments of the tree in tb_hnodes (rt_winding.hpp: 16 floats per node slot), made by the first
+    // call after anything that changed the tree (moments_dirty); its counting instantiation's five words (hrt_testing.h)
+    DevBuf<float> tb_moments;
+    bool moments_dirty = true;
+    DevBuf<unsigned long long> winding_counts;
+    bool winding_count = false;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -292,7 +301,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -415,6 +424,7 @@ int upload_tri_tree(rt_renderer* r) {
     r->tb_n_nodes = (uint32_t)r->tri_tree.nodes.size();
     r->tb_n_order = (uint32_t)r->tri_tree.order.size();
     r->tri_tree_dirty = false;
+    r->moments_dirty = true;
     return RT_OK;
 }
 
@@ -1188,6 +1198,9 @@ void delete_buffers(rt_renderer* r) {
     r->tile_order.release();
     r->tile_lists.release();
     r->closest_counts.release();
+    r->winding_counts.release();
+    r->tb_moments.release();
+    r->moments_dirty = true;
     r->tile_lists_valid = false;
     r->order_scratch.release();
     r->cost_tiles = r->order_tiles = 0;
@@ -1401,6 +1414,7 @@ int rt_set_bvh(rt_renderer* r, const uint32_t sizes[2], const void* nodes32, uin
         std::copy(v, v + 9, &r->tri_aee[9 * (size_t)j]);
     }
     r->tri_tree_dirty = true;
+    r->moments_dirty = true;
     const std::vector<hrt_dev::MatDev> md = pack_materials(mats32, n_mats);
     // The sign-ordered copy (36 B per node) only where a kernel reads it: the heap-top kernels run for heaps of at
     // most 2^24 nodes (launch_frames, tri_small); a larger tree would pay up to ~2.4 GB of host and device memory
@@ -1533,6 +1547,7 @@ int rt_set_triangles_device_with(rt_renderer* r, const void* tris64_dev, uint32_
     r->tb_iterations = ploc_nodes ? (uint32_t)stat[10] : 0u;
     r->tb_flat = ploc_nodes ? (uint32_t)stat[11] : 0u;
     r->tri_tree_dirty = false;
+    r->moments_dirty = true;
     r->dev_geom = true;
     r->dev_n_mats = n_mats;
     r->bvh_n = 0;  // no reference heap: nothing reads one in this state (scene_params: tri_bvh)
@@ -1653,6 +1668,7 @@ int rt_refit_triangles_device(rt_renderer* r, const void* tris64_dev, uint32_t n
     swap_buffers(r->tris, r->lb_tris);
     swap_buffers(r->tri_geo, r->lb_geo);
     if (slots) swap_buffers(r->tb_hnodes, r->lb_hnodes);
+    r->moments_dirty = true;
     r->cost_learn = true;
     return RT_OK;
 }
@@ -2117,6 +2133,200 @@ int rt_testing_get_closest_counts(rt_renderer* r, uint64_t out[4]) {
     return RT_OK;
 }
 
+// ---- winding numbers (include/hrt.h; rt_winding.hip k_winding / k_tree_moments, rt_winding.hpp the function) ----
+namespace {
+// The moments of the live tree in tb_moments, made when something changed the tree since they were made last. Device
+// geometry: the climb over tb_parent in the build's scratch (arrival counters and box slots; nothing a build or a refit
+// keeps between calls). The host SAH tree has no parent links on the device: the host mirror's records are uploaded.
+int ensure_moments(rt_renderer* r) {
+    if (!r->moments_dirty && r->tb_moments.ptr) return RT_OK;
+    const uint32_t slots = r->tb_n_nodes, root = r->tri_tree.root_word;
+    if ((root & hrt_winding::LEAF_BIT) != 0u || slots == 0u) {  // a tree without nodes: the flat definition answers
+        r->moments_dirty = false;
+        return ensure(r->tb_moments, hrt_winding::REC_FLOATS);
+    }
+    if (root >= slots || r->tb_hnodes.cap < 2 * (size_t)slots)
+        return fail(RT_ERR_STATE, "rt_winding_numbers: the tree is not consistent");
+    if (int rc = ensure(r->tb_moments, hrt_winding::REC_FLOATS * (size_t)slots)) return rc;
+    if (r->dev_geom) {
+        if (!r->tb_parent.ptr || r->tb_parent.cap < slots)
+            return fail(RT_ERR_STATE, "rt_winding_numbers: the device tree has no parent links");
+        int rc = ensure(r->lb_arrivals, slots);
+        if (!rc) rc = ensure(r->lb_boxes, 2 * (size_t)slots * hrt_winding::SUM_WORDS);
+        if (rc) return rc;
+        hrt_winding::MomentsLaunch a{};
+        a.hnodes = (const hrt_winding::U4*)r->tb_hnodes.ptr;
+        a.order = r->tb_order.ptr;
+        a.geo = r->tri_geo.ptr;
+        a.parent = r->tb_parent.ptr;
+        a.slots = slots;
+        for (int k = 0; k < 3; k++) a.rc[k] = r->tri_tree.root_center[k];
+        a.sums = (unsigned long long*)r->lb_boxes.ptr;
+        a.arrivals = r->lb_arrivals.ptr;
+        a.moments = r->tb_moments.ptr;
+        HIP_TRY(hrt_launch_tree_moments(a, r->stream));
+    } else {
+        const std::vector<uint4> hpacked = pack_bvh_hnodes(r->tri_tree.nodes, r->tri_tree.root_center);
+        hrt_winding::Tree T{};
+        T.hnodes = (const hrt_winding::U4*)hpacked.data();
+        T.order = r->tri_tree.order.data();
+        T.geo = r->tri_aee.data();
+        T.m = (uint32_t)(r->tri_aee.size() / 9);
+        T.root = root;
+        for (int k = 0; k < 3; k++) T.rc[k] = r->tri_tree.root_center[k];
+        std::vector<float> rec(hrt_winding::REC_FLOATS * (size_t)slots);
+        if (hpacked.size() < 2 * (size_t)slots || !hrt_winding::host_moments(T, slots, r->tri_tree.order.size(), rec.data()))
+            return fail(RT_ERR_STATE, "rt_winding_numbers: the host tree is not consistent");
+        HIP_TRY(hipMemcpyAsync(r->tb_moments.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, r->stream));
+        HIP_TRY(hipStreamSynchronize(r->stream));  // (rec leaves scope)
+    }
+    r->moments_dirty = false;
+    return RT_OK;
+}
+
+// The host mirrors' tree argument, copied (no alignment asked of the caller) and checked as far as a size can be.
+struct HostWindingTree {
+    std::vector<float> aee;
+    std::vector<hrt_winding::U4> nodes;
+    std::vector<uint32_t> ord;
+    hrt_winding::Tree T{};
+    int rc = RT_OK;
+    HostWindingTree(const char* who, const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots,
+                    const uint32_t* order, size_t n_order, uint32_t root_word, const float root[4]) {
+        const std::string w(who);
+        if (n_tris && !tris64) rc = fail(RT_ERR_ARG, w + ": null triangles");
+        else if (node_slots && (!hnodes || !root)) rc = fail(RT_ERR_ARG, w + ": null nodes or root");
+        else if (n_order && !order) rc = fail(RT_ERR_ARG, w + ": null order");
+        else if (node_slots >= (1u << 26) || n_order > (1u << 26)) rc = fail(RT_ERR_ARG, w + ": 2^26 or more node slots or positions");
+        else if (node_slots && (root_word & hrt_winding::LEAF_BIT) == 0u && root_word >= node_slots)
+            rc = fail(RT_ERR_ARG, w + ": the root word names a node past node_slots");
+        if (rc) return;
+        aee_of_triangles(tris64, n_tris, aee);
+        nodes.resize(2 * node_slots);
+        if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
+        if (n_order) ord.assign(order, order + n_order);
+        T.hnodes = nodes.data();
+        T.order = ord.data();
+        T.geo = aee.data();
+        T.m = n_tris;
+        T.root = node_slots ? root_word : hrt_winding::LEAF_BIT;  // (no nodes: the flat definition)
+        if (node_slots) {
+            for (int k = 0; k < 3; k++) T.rc[k] = root[k];
+            T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
+        }
+    }
+};
+}  // namespace
+
+int rt_winding_numbers(rt_renderer* r, const void* points_dev, uint32_t n, float beta, void* w_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_winding_numbers: null");
+    if (n == 0) return RT_OK;
+    if (!points_dev || !w_dev) return fail(RT_ERR_ARG, "rt_winding_numbers: null buffer");
+    if (misaligned(4, {points_dev, w_dev})) return fail(RT_ERR_ARG, "rt_winding_numbers: points and w must be 4-byte aligned");
+    if (!hrt_winding::beta_ok(beta))
+        return fail(RT_ERR_ARG, "rt_winding_numbers: beta must be 0 (the default 2.0) or at least 1 (+inf: no dipoles)");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_winding_numbers: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_winding_numbers: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    if (q.rc) return q.rc;
+    if (int rc = ensure_moments(r)) return rc;
+    hrt_winding::Launch a{};
+    a.tree.hnodes = (const hrt_winding::U4*)q.P.tb_hnodes;
+    a.tree.moments = r->tb_moments.ptr;
+    a.tree.order = q.P.tb_order;
+    a.tree.geo = q.P.tri_geo;
+    a.tree.m = q.P.m;
+    a.tree.root = q.P.tb_root;
+    for (int k = 0; k < 3; k++) a.tree.rc[k] = q.P.tb_rc[k];
+    a.tree.rr_h = q.P.tb_rr_h;
+    a.points = (const float*)points_dev;
+    a.out = (float*)w_dev;
+    a.n = n;
+    a.beta = beta;
+    if (r->winding_count) {
+        if (int rc = ensure(r->winding_counts, 5)) return rc;
+        HIP_TRY(hipMemsetAsync(r->winding_counts.ptr, 0, 5 * sizeof(unsigned long long), r->stream));
+        a.counts = r->winding_counts.ptr;
+    }
+    HIP_TRY(hrt_launch_winding(a, r->winding_count, r->stream));
+    return RT_OK;
+}
+
+// The moments on the host (rt_winding.hpp host_moments): pure CPU, no device.
+int rt_host_tree_moments(const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots, const uint32_t* order,
+                         size_t n_order, uint32_t root_word, const float root[4], void* moments_out, size_t moment_cap) {
+    HostWindingTree H("rt_host_tree_moments", tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    if (H.rc) return H.rc;
+    if (node_slots == 0) return RT_OK;  // a tree without nodes has no records
+    if (moment_cap < node_slots) return fail(RT_ERR_ARG, "rt_host_tree_moments: moment_cap is below node_slots");
+    if (!moments_out) return fail(RT_ERR_ARG, "rt_host_tree_moments: null output");
+    std::vector<float> rec(hrt_winding::REC_FLOATS * node_slots);
+    if (!hrt_winding::host_moments(H.T, node_slots, n_order, rec.data()))
+        return fail(RT_ERR_ARG, "rt_host_tree_moments: the nodes are not a tree over order and the triangles");
+    std::memcpy(moments_out, rec.data(), rec.size() * sizeof(float));
+    return RT_OK;
+}
+
+// The query on the host (rt_winding.hpp host_winding): pure CPU, no device; the bytes the device writes for that tree.
+int rt_host_winding_numbers(const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots, const uint32_t* order,
+                            size_t n_order, uint32_t root_word, const float root[4], const float* points, uint32_t n,
+                            float beta, float* w_out) {
+    if (!hrt_winding::beta_ok(beta))
+        return fail(RT_ERR_ARG, "rt_host_winding_numbers: beta must be 0 (the default 2.0) or at least 1 (+inf: no dipoles)");
+    if (n && (!points || !w_out)) return fail(RT_ERR_ARG, "rt_host_winding_numbers: null points or w_out");
+    HostWindingTree H("rt_host_winding_numbers", tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    if (H.rc) return H.rc;
+    std::vector<float> rec(hrt_winding::REC_FLOATS * std::max<size_t>(node_slots, 1));
+    if (node_slots && !hrt_winding::host_moments(H.T, node_slots, n_order, rec.data()))
+        return fail(RT_ERR_ARG, "rt_host_winding_numbers: the nodes are not a tree over order and the triangles");
+    H.T.moments = rec.data();
+    hrt_winding::host_winding(H.T, points, n, beta, w_out);
+    return RT_OK;
+}
+
+int rt_testing_set_winding_count(rt_renderer* r, uint32_t on) {
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_winding_count: null");
+    r->winding_count = on != 0u;
+    return RT_OK;
+}
+
+int rt_testing_get_winding_counts(rt_renderer* r, uint64_t out[5]) {
+    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_winding_counts: null");
+    for (int k = 0; k < 5; k++) out[k] = 0;
+    if (!r->winding_counts.ptr) return RT_OK;
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    HIP_TRY(hipMemcpyAsync(out, r->winding_counts.ptr, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+int rt_testing_winding_atan2(const float* y, const float* x, uint32_t n, float* out) {
+    if (n && (!y || !x || !out)) return fail(RT_ERR_ARG, "rt_testing_winding_atan2: null");
+    for (uint32_t i = 0; i < n; i++) out[i] = hrt_winding::atan2_f32(y[i], x[i]);
+    return RT_OK;
+}
+
+int rt_testing_get_tree_moments(rt_renderer* r, void* moments_out, size_t moment_cap, size_t* count) {
+    if (!r || !count) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: null");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_testing_get_tree_moments: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
+    if (int rc = ensure_moments(r)) return rc;
+    const size_t slots = (r->tri_tree.root_word & hrt_winding::LEAF_BIT) != 0u ? 0u : r->tb_n_nodes;
+    *count = slots;
+    if (moment_cap == 0) return RT_OK;
+    if (moment_cap < slots) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: moment_cap is too small");
+    if (slots && !moments_out) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: null output");
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (slots) HIP_TRY(hipMemcpy(moments_out, r->tb_moments.ptr, slots * 64u, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_regroup_paths(rt_renderer* r, const rt_regroup* io, uint32_t n) {
     if (!r) return fail(RT_ERR_ARG, "rt_regroup_paths: null");
     if (n == 0) return RT_OK;
@@ -2292,6 +2502,8 @@ int rt_release_scratch(rt_renderer* r) {
     r->lb_arrivals.release();
     r->lb_boxes.release();
     r->lb_stat.release();
+    r->tb_moments.release();  // (rt_winding_numbers makes the moments again)
+    r->moments_dirty = true;
     return RT_OK;
 }
 

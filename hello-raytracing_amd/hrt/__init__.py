@@ -9,7 +9,8 @@ from ._lib import (REGROUP_CELL_OCTANT, REGROUP_KEYS, REGROUP_TILE, RtRegroup, R
 from .scene import (CAMERA_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
                     Renderer, SceneSphere, SceneTris, Sphere, Tree, Vec3, compare_ppm_images, f32,
-                    closest_points_host, lbvh_build, lbvh_cost, lbvh_refit, ppm_from_image, read_asset, render_ppm, spheres_array)
+                    closest_points_host, lbvh_build, lbvh_cost, lbvh_refit, ppm_from_image, read_asset, render_ppm, spheres_array,
+                    tree_moments_host, winding_numbers_host)
 
 
 def device_count() -> int:
@@ -104,4 +105,5 @@ __all__ = [
     "read_asset", "render_ppm", "spheres_array", "device_count", "check_uniform_guards", "UGUARD_COLUMNS", "UGUARD_HELPERS",
     "sphere_bvh_leaves", "regroup_keys", "REGROUP_CELL_OCTANT", "REGROUP_KEYS", "REGROUP_TILE", "RtRegroup",
     "lbvh_build", "lbvh_refit", "lbvh_cost", "CLOSEST_DTYPE", "closest_points_host",
+    "tree_moments_host", "winding_numbers_host",
 ]

@@ -653,6 +653,59 @@ class Renderer:
         check(lib().rt_testing_get_closest_counts(self._h, c), "testing_get_closest_counts")
         return np.array(list(c), dtype=np.uint64)
 
+    def winding_numbers(self, points, beta: float = 0.0):
+        """rt_winding_numbers: the generalized winding number of the renderer's triangles at each point (triangle and
+        mixed programs, with device geometry or tri_bvh = 1; the spheres of the mixed program do not answer): 1 inside a
+        closed mesh wound outward, 0 outside, in between where the mesh is open. points as closest_points; beta: the
+        far-field factor (0 = the default 2.0, at least 1 otherwise, float("inf") sums every triangle exactly). Returns
+        an (N,) float32 tensor on the renderer's device; a non-finite point gives NaN."""
+        import torch
+
+        who = "winding_numbers"
+        pts = self._rays_on_device(who, points, "points")
+        n = int(pts.shape[0])
+        if n >= 1 << 32:
+            raise ValueError(f"{who}: at most 2^32 - 1 points per call")
+        out = torch.empty((n,), dtype=torch.float32, device=self._torch_device())
+        self._query(who, lib().rt_winding_numbers, _ptr(pts), n, C.c_float(beta), _ptr(out))
+        return out
+
+    def signed_distance(self, points, beta: float = 0.0) -> dict:
+        """closest_points and winding_numbers on the same points, composed with torch ops: the fields of closest_points,
+        winding (the raw w), inside = |w| >= 0.5 (|w|, so that a mesh wound inward works too) and distance = sqrt(d2),
+        negative where inside is true."""
+        import torch
+
+        pts = self._rays_on_device("signed_distance", points, "points")
+        out = self.closest_points(pts)
+        w = self.winding_numbers(pts, beta)
+        inside = w.abs() >= 0.5
+        dist = torch.sqrt(out["d2"])
+        out.update(winding=w, inside=inside, distance=torch.where(inside, -dist, dist))
+        return out
+
+    def set_winding_count(self, on: bool) -> None:
+        """Test-only: winding_numbers runs the counting instantiation of its kernel (include/hrt_testing.h
+        rt_testing_set_winding_count)."""
+        check(lib().rt_testing_set_winding_count(self._h, 1 if on else 0), "testing_set_winding_count")
+
+    def winding_counts(self) -> np.ndarray:
+        """Test-only: uint64[5] of the last counted winding_numbers call: queries, triangle terms, dipole terms, stack
+        overflows, uncovered points (include/hrt_testing.h rt_testing_get_winding_counts)."""
+        c = (C.c_uint64 * 5)()
+        check(lib().rt_testing_get_winding_counts(self._h, c), "testing_get_winding_counts")
+        return np.array(list(c), dtype=np.uint64)
+
+    def tree_moments(self) -> np.ndarray:
+        """Test-only (include/hrt_testing.h rt_testing_get_tree_moments): the moments winding_numbers reads, (node slots,
+        16) float32, made first if the tree changed since."""
+        n = C.c_size_t(0)
+        check(lib().rt_testing_get_tree_moments(self._h, None, 0, C.byref(n)), "testing_get_tree_moments")
+        out = np.zeros((int(n.value), 16), dtype=np.float32)
+        if out.size:
+            check(lib().rt_testing_get_tree_moments(self._h, out.ctypes.data, len(out), C.byref(n)), "testing_get_tree_moments")
+        return out
+
     def primary_rays(self, time: int):
         """rt_primary_rays: (origins, dirs), each (local_rows, width, 3) float32 on the renderer's device — the rays the
         frame drawn at `time` traces first for each of this renderer's pixels."""
@@ -977,6 +1030,45 @@ def closest_points_host(triangles: np.ndarray, points: np.ndarray, max_dist2=Non
     check(lib().rt_host_closest_points(t.ctypes.data if m else None, m, p.ctypes.data_as(_lib._PF) if n else None,
                                        cap.ctypes.data_as(_lib._PF) if cap is not None and n else None, n,
                                        out.ctypes.data if n else None), "rt_host_closest_points")
+    return out
+
+
+def _winding_tree_args(triangles, tree):
+    """(triangles, m, nodes, slots, order, n_order, root word, root) as the two host calls take them; tree: a dict of
+    lbvh_build / lbvh_refit / Renderer.tri_tree, or None for the flat definition."""
+    t = _triangle_records(triangles)
+    m = len(t)
+    if tree is None:
+        nodes, order = np.zeros((0, 8), dtype=np.uint32), np.zeros((0,), dtype=np.uint32)
+        word, root = 0x80000000, np.zeros((4,), dtype=np.float32)
+    else:
+        nodes = np.ascontiguousarray(tree["nodes"], dtype=np.uint32).reshape(-1, 8)
+        order = np.ascontiguousarray(tree["order"], dtype=np.uint32)
+        word, root = int(tree["info"][3]), np.ascontiguousarray(tree["root"], dtype=np.float32)
+    keep = (t, nodes, order, root)
+    return keep, (t.ctypes.data if m else None, m, nodes.ctypes.data if len(nodes) else None, len(nodes),
+                  order.ctypes.data_as(_lib._PU32) if len(order) else None, len(order), word, root.ctypes.data_as(_lib._PF))
+
+
+def tree_moments_host(triangles: np.ndarray, tree: dict) -> np.ndarray:
+    """rt_host_tree_moments (include/hrt.h): the moments of a tree dict's subtrees on the host, no device: (node slots, 16)
+    float32, per child c xyz (relative to the root centre), N xyz, 0, 0. A tree without nodes gives no records."""
+    keep, args = _winding_tree_args(triangles, tree)
+    out = np.zeros((len(keep[1]), 16), dtype=np.float32)
+    check(lib().rt_host_tree_moments(*args, out.ctypes.data if out.size else None, len(out)), "rt_host_tree_moments")
+    return out
+
+
+def winding_numbers_host(triangles: np.ndarray, tree, points: np.ndarray, beta: float = 0.0) -> np.ndarray:
+    """rt_host_winding_numbers (include/hrt.h): Renderer.winding_numbers on the host, no device, for the tree dict `tree`
+    (the bytes the device writes for that tree), or the flat definition — every triangle, no dipoles — with tree = None.
+    Returns (n,) float32."""
+    keep, args = _winding_tree_args(triangles, tree)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = len(p)
+    out = np.zeros((n,), dtype=np.float32)
+    check(lib().rt_host_winding_numbers(*args, p.ctypes.data_as(_lib._PF) if n else None, n, C.c_float(beta),
+                                        out.ctypes.data_as(_lib._PF) if n else None), "rt_host_winding_numbers")
     return out
 
 

@@ -579,6 +579,58 @@ int rt_closest_points(rt_renderer *r, const void *points_dev, const void *maxd2_
 int rt_host_closest_points(const void *tris64, uint32_t n_tris, const float *points, const float *maxd2,
                            uint32_t n, void *out32);
 
+/* Inside or outside: the generalized winding number of the triangle set at each of the caller's points (Jacobson et al.
+ * 2013), w(p) = (1 / 4 pi) sum_j Omega_j(p) with Omega_j the signed solid angle of triangle j seen from p. 1 inside a
+ * closed mesh wound outward (-1 for one wound inward), 0 outside, and in between where the mesh is open; cracks, holes
+ * and overlapping shells do not break it, which ray parity and pseudo-normals cannot say of the (a, e1, e2) records kept
+ * here. With rt_closest_points it gives a signed distance: negative where |w| >= 0.5.
+ * points_dev: n x 3 f32, packed (12-byte stride, 4-byte aligned); w_dev: n f32 (4-byte aligned); exactly 4 n bytes are
+ * written. Both are device memory on the renderer's GPU. Asynchronous on the renderer's stream, exactly as
+ * rt_closest_points is.
+ * beta is the far-field factor: 0 means the default 2.0; a value >= 1 is taken as it is; +inf sums every triangle of the
+ * tree exactly, with no dipoles; NaN, a negative value or a value in (0, 1) is RT_ERR_ARG. A larger beta is more accurate
+ * and slower (DESIGN.md §7f has measured errors: up to 0.04 to 0.07 at beta = 2 and 0.01 to 0.04 at beta = 3 on the project's
+ * meshes, against 0.25 that the sign can bear).
+ * The answer is a pure function of the tree bytes, the (a, e1, e2) records, the point and beta, and csrc/rt_winding.hpp is
+ * that function for host and device alike (f32 triangle terms, one f64 accumulator per query, a written-out atan2, no
+ * FMA, every operation rounded once in a fixed order):
+ *   - the triangle term is Van Oosterom and Strackee's atan2 form on x0 = a - p, x1 = x0 + e1, x2 = x0 + e2, scaled by
+ *     an exact power of two first; finite input never gives NaN or infinity; a triangle with a non-finite a, e1 or e2
+ *     contributes 0;
+ *   - per child of every node the tree carries two moments, the area-weighted normal sum N and the area-weighted centroid
+ *     c (rt_host_tree_moments); a child whose c is further from the point than beta times the radius R of its box about
+ *     c is taken whole as the dipole N . d / (4 L^3) (Barill et al. 2018, first order); otherwise a node child is
+ *     descended and a leaf child's triangles are summed;
+ *   - the flat definition — the triangle term over all triangles in index order, no dipoles — answers for a tree
+ *     without nodes (four triangles or fewer), for a point outside the range the walk covers (rt_closest_points' D
+ *     outside [2^-40, 2^60]) and for a query that overflows the walk's stack of 24 (a tree deeper than 24 can send
+ *     points there, slow and correct);
+ *   - a non-finite point gives the quiet NaN 0x7FC00000.
+ * rt_host_winding_numbers is that function on the host, and the device returns its bytes for the same tree
+ * (rt_host_lbvh_build_with gives the device builders' trees).
+ * The moments are made by the first call after anything that changed the tree (rt_set_bvh, a device build or refit,
+ * rt_release_scratch) and kept in device memory that rt_stats.device_bytes counts (64 B per node slot; rt_release_scratch frees it).
+ * Programs and states are rt_closest_points': RT_ERR_ARG in the sphere program, for n > 0 with a null or misaligned
+ * buffer, and for a bad beta; RT_ERR_STATE without a triangle tree (device geometry or rt_params.tri_bvh = 1; a host SAH
+ * tree not built yet is built first). The spheres of the mixed program do not answer. n = 0 returns RT_OK and launches
+ * nothing. It touches no image, frame count, stats, raw counters or learnt cost order. */
+int rt_winding_numbers(rt_renderer *r, const void *points_dev, uint32_t n, float beta, void *w_dev);
+/* The moments on the host: pure CPU, no device. tris64: n_tris Triangle records (64 B each; no alignment asked). hnodes,
+ * node_slots, order, n_order, root_word and root (centre xyz, radius) are what rt_host_lbvh_build_with or
+ * rt_testing_get_tri_tree return. moments_out: 64 B per node slot — per child {c[3] relative to the root centre, N[3], 0,
+ * 0} as f32 —, the slots no child word names zero; moment_cap in slots. A tree without nodes (node_slots = 0) writes
+ * nothing. RT_ERR_ARG: a null argument that is needed, moment_cap < node_slots, or bytes that are not a tree over order
+ * and the triangles (a child word past node_slots or named twice, a leaf past n_order, an order entry past n_tris). */
+int rt_host_tree_moments(const void *tris64, uint32_t n_tris, const void *hnodes, size_t node_slots,
+                         const uint32_t *order, size_t n_order, uint32_t root_word, const float root[4],
+                         void *moments_out, size_t moment_cap);
+/* The query on the host: pure CPU, no device; the tree arguments as above. node_slots = 0 with a null hnodes gives the
+ * flat definition (order, root_word and root are not read). points: n x 3 f32; w_out: n f32. RT_ERR_ARG as above, for a
+ * bad beta, and for a null points or w_out with n > 0. */
+int rt_host_winding_numbers(const void *tris64, uint32_t n_tris, const void *hnodes, size_t node_slots,
+                            const uint32_t *order, size_t n_order, uint32_t root_word, const float root[4],
+                            const float *points, uint32_t n, float beta, float *w_out);
+
 /* Test-only entry points (fault injection) are declared in hrt_testing.h, not here: they are not part of
  * the drop-in surface. */
 
@@ -653,7 +705,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
                              rt_host_regroup_keys, then rt_set_triangles_device / rt_host_lbvh_build, then
                              rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, then
                              rt_set_triangles_device_with / rt_host_lbvh_build_with / rt_host_lbvh_refit_with /
-                             rt_get_tri_tree_info, then rt_closest_points / rt_host_closest_points, came
+                             rt_get_tri_tree_info, then rt_closest_points / rt_host_closest_points, then rt_winding_numbers /
+                             rt_host_tree_moments / rt_host_winding_numbers, came
                              later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 

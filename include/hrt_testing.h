@@ -91,6 +91,21 @@ int rt_testing_set_closest_count(rt_renderer *r, uint32_t on);
  *   that took that loop instead of the walk because the walk's error bound does not cover the point}. */
 int rt_testing_get_closest_counts(rt_renderer *r, uint64_t out[4]);
 
+/* on != 0: rt_winding_numbers launches the counting instantiation of its kernel (k_winding<true>: the same walk and the
+ *   same bytes, plus five sums per wave added to five words with one agent-scope atomic each); 0: the product kernel,
+ *   which holds no counting code. Stays set until changed; a new renderer starts with 0. */
+int rt_testing_set_winding_count(rt_renderer *r, uint32_t on);
+/* Blocking: the five words of the last rt_winding_numbers call made with counting on (zeros before the first): {queries,
+ *   triangle terms (the flat definition's m included where a query took it), dipole terms, queries that overflowed the
+ *   walk's stack, points the walk does not cover (non-finite ones included)}. */
+int rt_testing_get_winding_counts(rt_renderer *r, uint64_t out[5]);
+/* Blocking: the moments rt_winding_numbers reads (made first if the tree changed since), 64 B per node slot as
+ *   rt_host_tree_moments writes them. *count = node slots (0 for a tree without nodes); moment_cap = 0 asks for the count
+ *   alone, a smaller cap otherwise is RT_ERR_ARG. Programs and states as rt_winding_numbers. */
+int rt_testing_get_tree_moments(rt_renderer *r, void *moments_out, size_t moment_cap, size_t *count);
+/* Pure CPU: out[i] = csrc/rt_winding.hpp's written-out atan2 of (y[i], x[i]), the function host and device compile. */
+int rt_testing_winding_atan2(const float *y, const float *x, uint32_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 #include "rt_closest.hpp"
 #include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
+#include "rt_multihit.hpp"
 #include "rt_winding.hpp"
 #include "rt_tile_lists.hpp"
 
@@ -49,6 +50,7 @@ hipError_t hrt_launch_tri_tree_cost(const void* hnodes, uint32_t slots, uint32_t
 hipError_t hrt_launch_closest(const hrt_closest::Launch& a, bool count, hipStream_t stream);      // rt_closest.hip
 hipError_t hrt_launch_winding(const hrt_winding::Launch& a, bool count, hipStream_t stream);      // rt_winding.hip
 hipError_t hrt_launch_tree_moments(const hrt_winding::MomentsLaunch& a, hipStream_t stream);      // rt_winding.hip
+hipError_t hrt_launch_multihit(const hrt_multihit::Launch& a, bool stats, hipStream_t stream);    // rt_multihit.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -272,6 +274,9 @@ struct rt_renderer {
     bool moments_dirty = true;
     DevBuf<unsigned long long> winding_counts;
     bool winding_count = false;
+    // rt_cast_rays_multi's counting instantiation (hrt_testing.h): selected by multihit_count, its four words
+    DevBuf<unsigned long long> multihit_counts;
+    bool multihit_count = false;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -301,7 +306,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + multihit_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -1199,6 +1204,7 @@ void delete_buffers(rt_renderer* r) {
     r->tile_lists.release();
     r->closest_counts.release();
     r->winding_counts.release();
+    r->multihit_counts.release();
     r->tb_moments.release();
     r->moments_dirty = true;
     r->tile_lists_valid = false;
@@ -2324,6 +2330,107 @@ int rt_testing_get_tree_moments(rt_renderer* r, void* moments_out, size_t moment
     if (slots && !moments_out) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: null output");
     HIP_TRY(hipStreamSynchronize(r->stream));
     if (slots) HIP_TRY(hipMemcpy(moments_out, r->tb_moments.ptr, slots * 64u, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// ---- multi-hit ray queries (include/hrt.h; rt_multihit.hip k_cast_rays_multi, rt_multihit.hpp the function) ----
+int rt_cast_rays_multi(rt_renderer* r, const void* origins_dev, const void* dirs_dev, const void* tmax_dev, const void* after_dev,
+                       uint32_t n, uint32_t k, void* hits_dev, void* counts_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_cast_rays_multi: null");
+    if (k > RT_MULTI_HIT_MAX_K) return fail(RT_ERR_ARG, "rt_cast_rays_multi: k exceeds RT_MULTI_HIT_MAX_K");
+    if (n == 0) return RT_OK;
+    if (k == 0 && !counts_dev) return fail(RT_ERR_ARG, "rt_cast_rays_multi: k = 0 needs counts");
+    if (k > 0 && !hits_dev) return fail(RT_ERR_ARG, "rt_cast_rays_multi: k > 0 needs hits");
+    if (!origins_dev || !dirs_dev) return fail(RT_ERR_ARG, "rt_cast_rays_multi: null buffer");
+    if (misaligned(16, {hits_dev}) || misaligned(4, {origins_dev, dirs_dev, tmax_dev, after_dev, counts_dev}))
+        return fail(RT_ERR_ARG, "rt_cast_rays_multi: hits must be 16-byte aligned, every other buffer 4-byte aligned");
+    static_assert(sizeof(rt_multi_hit) == 16, "rt_multi_hit: one 16-byte store per record (k_cast_rays_multi)");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_cast_rays_multi: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_cast_rays_multi: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    if (q.rc) return q.rc;
+    hrt_multihit::Launch a{};
+    a.tree.hnodes = (const hrt_multihit::U4*)q.P.tb_hnodes;
+    a.tree.order = q.P.tb_order;
+    a.tree.geo = q.P.tri_geo;
+    a.tree.m = q.P.m;
+    a.tree.root = q.P.tb_root;
+    a.tree.flat = 0u;
+    for (int c = 0; c < 3; c++) a.tree.rc[c] = q.P.tb_rc[c];
+    a.tree.rr_h = q.P.tb_rr_h;
+    a.origins = (const float*)origins_dev;
+    a.dirs = (const float*)dirs_dev;
+    a.tmax = (const float*)tmax_dev;
+    a.after = (const hrt_multihit::Hit*)after_dev;
+    a.hits = hits_dev;
+    a.counts = (uint32_t*)counts_dev;
+    a.n = n;
+    a.k = k;
+    if (r->multihit_count) {
+        if (int rc = ensure(r->multihit_counts, 4)) return rc;
+        HIP_TRY(hipMemsetAsync(r->multihit_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
+        a.stats = r->multihit_counts.ptr;
+    }
+    HIP_TRY(hrt_launch_multihit(a, r->multihit_count, r->stream));
+    return RT_OK;
+}
+
+// The query on the host (rt_multihit.hpp host_multi): pure CPU, no device; the bytes the device writes for that tree.
+int rt_host_cast_rays_multi(const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots, const uint32_t* order,
+                            size_t n_order, uint32_t root_word, const float root[4], const float* origins, const float* dirs,
+                            const float* tmax, const void* after16, uint32_t n, uint32_t k, void* hits16, uint32_t* counts) {
+    const char* const who = "rt_host_cast_rays_multi";
+    if (k > RT_MULTI_HIT_MAX_K) return fail(RT_ERR_ARG, std::string(who) + ": k exceeds RT_MULTI_HIT_MAX_K");
+    if (k == 0 && !counts) return fail(RT_ERR_ARG, std::string(who) + ": k = 0 needs counts");
+    if (n && (!origins || !dirs || (k && !hits16))) return fail(RT_ERR_ARG, std::string(who) + ": null rays or hits");
+    if (n_tris && !tris64) return fail(RT_ERR_ARG, std::string(who) + ": null triangles");
+    if (!root) return fail(RT_ERR_ARG, std::string(who) + ": null root");
+    if ((node_slots != 0) != (hnodes != nullptr)) return fail(RT_ERR_ARG, std::string(who) + ": nodes and node_slots disagree");
+    if (node_slots && n_order && !order) return fail(RT_ERR_ARG, std::string(who) + ": null order");
+    if (node_slots >= (1u << 26) || n_order > (1u << 26))
+        return fail(RT_ERR_ARG, std::string(who) + ": 2^26 or more node slots or positions");
+    std::vector<float> aee;
+    aee_of_triangles(tris64, n_tris, aee);
+    std::vector<hrt_multihit::U4> nodes(2 * node_slots);  // copied: no alignment asked of the caller
+    if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
+    std::vector<uint32_t> ord;
+    if (node_slots && n_order) ord.assign(order, order + n_order);
+    hrt_multihit::Tree T{};
+    T.hnodes = nodes.data();
+    T.order = ord.data();
+    T.geo = aee.data();
+    T.m = n_tris;
+    T.root = root_word;
+    T.flat = node_slots ? 0u : 1u;
+    for (int c = 0; c < 3; c++) T.rc[c] = root[c];
+    T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
+    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, ord.size()))
+        return fail(RT_ERR_ARG, std::string(who) + ": the nodes are not a tree over order and the triangles");
+    std::vector<hrt_multihit::Hit> after, out((size_t)n * k);
+    if (after16 && n) {
+        after.resize(n);
+        std::memcpy(after.data(), after16, (size_t)n * sizeof(hrt_multihit::Hit));
+    }
+    hrt_multihit::host_multi(T, origins, dirs, tmax, after16 ? after.data() : nullptr, n, k, out.data(), counts);
+    if (!out.empty()) std::memcpy(hits16, out.data(), out.size() * sizeof(hrt_multihit::Hit));
+    return RT_OK;
+}
+
+int rt_testing_set_multihit_count(rt_renderer* r, uint32_t on) {
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_multihit_count: null");
+    r->multihit_count = on != 0u;
+    return RT_OK;
+}
+
+int rt_testing_get_multihit_counts(rt_renderer* r, uint64_t out[4]) {
+    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_multihit_counts: null");
+    for (int c = 0; c < 4; c++) out[c] = 0;
+    if (!r->multihit_counts.ptr) return RT_OK;
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    HIP_TRY(hipMemcpyAsync(out, r->multihit_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }
 

@@ -50,6 +50,10 @@ assert HIT_DTYPE.itemsize == 32
 CLOSEST_DTYPE = np.dtype([("d2", "<f4"), ("prim", "<i4"), ("p", "<f4", 3), ("v", "<f4"), ("w", "<f4"),
                           ("reserved", "<u4")])
 assert CLOSEST_DTYPE.itemsize == 32
+# rt_multi_hit (include/hrt.h): one record of rt_cast_rays_multi
+MULTI_HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4")])
+MULTI_HIT_MAX_K = 16
+assert MULTI_HIT_DTYPE.itemsize == 16
 assert CAMERA_DTYPE.itemsize == 80 and MATERIAL_DTYPE.itemsize == 32 and SPHERE_DTYPE.itemsize == 48
 assert NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 64
 
@@ -653,6 +657,124 @@ class Renderer:
         check(lib().rt_testing_get_closest_counts(self._h, c), "testing_get_closest_counts")
         return np.array(list(c), dtype=np.uint64)
 
+    def _per_ray_f32(self, who: str, what: str, x, n: int):
+        """An optional per-ray float: None, a Python float for every ray, or an (n,) float32 numpy array or tensor on the
+        renderer's device, as a contiguous tensor there (or None)."""
+        import torch
+
+        if x is None:
+            return None
+        dev = self._torch_device()
+        if isinstance(x, (int, float)):
+            return torch.full((n,), float(x), dtype=torch.float32, device=dev)
+        if not torch.is_tensor(x):
+            x = np.asarray(x)
+            if x.dtype != np.float32:
+                raise ValueError(f"{who}: {what} must be float32, got {x.dtype}")
+            x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        if x.dtype != torch.float32 or tuple(x.shape) != (n,):
+            raise ValueError(f"{who}: {what} must be ({n},) float32, got {tuple(x.shape)} {x.dtype}")
+        if x.device != dev:
+            raise ValueError(f"{who}: {what} is on {x.device}, the renderer draws on {dev}")
+        return x.contiguous()
+
+    def cast_rays_multi_records(self, origins, dirs, k: int, tmax=None, after=None, counts: bool = False):
+        """rt_cast_rays_multi, the raw records: an (N, k, 4) int32 tensor on the renderer's device, one 16-byte
+        rt_multi_hit per ray and rank (MULTI_HIT_DTYPE on the host), and the (N,) int32 counts or None. origins, dirs,
+        tmax as occluded; after: None, or the cursors as an (N, 4) int32 tensor on the renderer's device (one record per
+        ray, e.g. records[:, -1]) or N MULTI_HIT_DTYPE numpy records. Synchronises torch's current stream before the call
+        and the renderer after it."""
+        import torch
+
+        who = "cast_rays_multi"
+        o, d, n = self._ray_pair(who, origins, dirs)
+        k = int(k)
+        if not 0 <= k <= MULTI_HIT_MAX_K:
+            raise ValueError(f"{who}: k must be 0 .. {MULTI_HIT_MAX_K}, got {k}")
+        if k == 0 and not counts:
+            raise ValueError(f"{who}: k = 0 needs counts = True")
+        dev = self._torch_device()
+        cap = self._per_ray_f32(who, "tmax", tmax, n)
+        cur = after
+        if cur is not None:
+            if not torch.is_tensor(cur):
+                cur = np.ascontiguousarray(cur, dtype=MULTI_HIT_DTYPE).reshape(-1)
+                cur = torch.from_numpy(cur.view(np.int32).reshape(-1, 4)).to(dev)
+            if cur.dtype != torch.int32 or tuple(cur.shape) != (n, 4):
+                raise ValueError(f"{who}: after must be ({n}, 4) int32 records, got {tuple(cur.shape)} {cur.dtype}")
+            if cur.device != dev:
+                raise ValueError(f"{who}: after is on {cur.device}, the renderer draws on {dev}")
+            cur = cur.contiguous()
+        hits = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        self._query(who, lib().rt_cast_rays_multi, _ptr(o), _ptr(d), _ptr(cap), _ptr(cur), n, k, _ptr(hits) if k else None,
+                    _ptr(cnt))
+        return hits, cnt
+
+    def cast_rays_multi(self, origins, dirs, k: int, tmax=None, after=None, counts: bool = False) -> dict:
+        """rt_cast_rays_multi: the k nearest triangles each ray passes through, in (t, prim) order — two triangles at the
+        same t are both listed — on the renderer's triangle tree (triangle and mixed programs, with device geometry or
+        tri_bvh = 1; the spheres of the mixed program do not answer). k: 0 .. 16; tmax as occluded (hits at t >= tmax are
+        left out); after: a cursor per ray, see cast_rays_multi_records — with each ray's last record of one call the next
+        call returns the next k hits. Returns torch tensors on the renderer's device: t (N, k) float32 (RT_T_MISS for an
+        unused rank), prim (N, k) int32 (-1 there), u, v (N, k) float32, records (N, k, 4) int32 (the raw records), and
+        with counts = True count (N,) int32, the number of all hits under tmax and beyond the cursor, not capped by k."""
+        import torch
+
+        rec, cnt = self.cast_rays_multi_records(origins, dirs, k, tmax, after, counts)
+        f = rec.view(torch.float32)
+        out = {"t": f[:, :, 0].clone(), "prim": rec[:, :, 1].clone(), "u": f[:, :, 2].clone(), "v": f[:, :, 3].clone(),
+               "records": rec}
+        if counts:
+            out["count"] = cnt
+        return out
+
+    def all_hits(self, origins, dirs, tmax=None):
+        """Every hit of every ray, ragged: one counting call (k = 0), then pages of 16 by cursor over the rays that still
+        have hits left. Returns (offsets, t, prim, u, v) on the renderer's device: offsets (N + 1,) int64, ray i's hits at
+        [offsets[i], offsets[i + 1]) of t (float32), prim (int32), u, v (float32), in (t, prim) order."""
+        import torch
+
+        who = "all_hits"
+        o, d, n = self._ray_pair(who, origins, dirs)
+        dev = self._torch_device()
+        cap = self._per_ray_f32(who, "tmax", tmax, n)
+        _, cnt = self.cast_rays_multi_records(o, d, 0, cap, None, True)
+        cnt = cnt.to(torch.int64)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=offsets[1:])
+        total = int(offsets[-1].item()) if n else 0
+        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        rays = torch.nonzero(cnt > 0).reshape(-1)
+        done = torch.zeros((n,), dtype=torch.int64, device=dev)
+        cursor = None
+        K = MULTI_HIT_MAX_K
+        rank = torch.arange(K, device=dev, dtype=torch.int64)
+        while rays.numel():
+            rec, _ = self.cast_rays_multi_records(o[rays], d[rays], K, None if cap is None else cap[rays], cursor, False)
+            left = (cnt[rays] - done[rays]).clamp(max=K)
+            take = rank[None, :] < left[:, None]
+            dst = (offsets[rays] + done[rays])[:, None] + rank[None, :]
+            out[dst[take]] = rec[take]
+            done[rays] += left
+            more = done[rays] < cnt[rays]
+            cursor = rec[more][:, K - 1, :].contiguous()
+            rays = rays[more]
+        f = out.view(torch.float32)
+        return offsets, f[:, 0].clone(), out[:, 1].clone(), f[:, 2].clone(), f[:, 3].clone()
+
+    def set_multihit_count(self, on: bool) -> None:
+        """Test-only: cast_rays_multi runs the counting instantiation of its kernel (include/hrt_testing.h
+        rt_testing_set_multihit_count)."""
+        check(lib().rt_testing_set_multihit_count(self._h, 1 if on else 0), "testing_set_multihit_count")
+
+    def multihit_counts(self) -> np.ndarray:
+        """Test-only: uint64[4] of the last counted cast_rays_multi call: queries, triangle tests, box tests, stack
+        overflows (include/hrt_testing.h rt_testing_get_multihit_counts)."""
+        c = (C.c_uint64 * 4)()
+        check(lib().rt_testing_get_multihit_counts(self._h, c), "testing_get_multihit_counts")
+        return np.array(list(c), dtype=np.uint64)
+
     def winding_numbers(self, points, beta: float = 0.0):
         """rt_winding_numbers: the generalized winding number of the renderer's triangles at each point (triangle and
         mixed programs, with device geometry or tri_bvh = 1; the spheres of the mixed program do not answer): 1 inside a
@@ -1070,6 +1192,45 @@ def winding_numbers_host(triangles: np.ndarray, tree, points: np.ndarray, beta: 
     check(lib().rt_host_winding_numbers(*args, p.ctypes.data_as(_lib._PF) if n else None, n, C.c_float(beta),
                                         out.ctypes.data_as(_lib._PF) if n else None), "rt_host_winding_numbers")
     return out
+
+
+def cast_rays_multi_host(triangles: np.ndarray, tree: dict, origins: np.ndarray, dirs: np.ndarray, k: int, tmax=None,
+                         after=None, counts: bool = False, flat: bool = False):
+    """rt_host_cast_rays_multi (include/hrt.h): Renderer.cast_rays_multi on the host, no device, for the tree dict `tree`
+    (lbvh_build / lbvh_refit / Renderer.tri_tree): the bytes the device writes for that tree. flat = True runs the flat
+    definition instead, a loop over all triangles in index order; only the tree's root (centre, radius) is read then.
+    tmax: None, a float for every ray, or (n,) float32; after: None or n MULTI_HIT_DTYPE records (t and prim are read).
+    Returns (n, k) MULTI_HIT_DTYPE records, and with counts = True a pair of them and (n,) uint32 counts (k = 0 needs
+    counts)."""
+    keep, args = _winding_tree_args(triangles, tree)
+    if flat:
+        args = args[:2] + (None, 0, None, 0, 0x80000000) + args[7:]
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n = len(o)
+    if o.shape != d.shape:
+        raise ValueError(f"cast_rays_multi_host: {o.shape} origins for {d.shape} directions")
+    cap = None
+    if tmax is not None:
+        cap = (np.full((n,), tmax, dtype=np.float32) if isinstance(tmax, (int, float))
+               else np.ascontiguousarray(tmax, dtype=np.float32))
+        if cap.shape != (n,):
+            raise ValueError(f"cast_rays_multi_host: tmax must be ({n},) float32, got {cap.shape}")
+    cur = None
+    if after is not None:
+        cur = np.ascontiguousarray(after, dtype=MULTI_HIT_DTYPE)
+        if cur.shape != (n,):
+            raise ValueError(f"cast_rays_multi_host: after must be ({n},) records, got {cur.shape}")
+    hits = np.zeros((n, k), dtype=MULTI_HIT_DTYPE)
+    cnt = np.zeros((n,), dtype=np.uint32) if counts else None
+    check(lib().rt_host_cast_rays_multi(*args, o.ctypes.data_as(_lib._PF) if n else None,
+                                        d.ctypes.data_as(_lib._PF) if n else None,
+                                        cap.ctypes.data_as(_lib._PF) if cap is not None and n else None,
+                                        cur.ctypes.data if cur is not None and n else None, n, k,
+                                        hits.ctypes.data if hits.size else None,
+                                        cnt.ctypes.data_as(_lib._PU32) if cnt is not None else None),
+          "rt_host_cast_rays_multi")
+    return (hits, cnt) if counts else hits
 
 
 def render_ppm(renderer: Renderer) -> str:

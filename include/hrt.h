@@ -631,6 +631,57 @@ int rt_host_winding_numbers(const void *tris64, uint32_t n_tris, const void *hno
                             const uint32_t *order, size_t n_order, uint32_t root_word, const float root[4],
                             const float *points, uint32_t n, float beta, float *w_out);
 
+/* Multi-hit ray queries (no reference counterpart): the k nearest triangles a ray passes through, in order, and the
+ * number of all of them — what a loop of rt_cast_rays from hit to hit cannot give (it walks once per layer and drops the
+ * second of two triangles hit at the same t). Triangle and mixed programs, on the triangle tree rt_closest_points walks.
+ * origins_dev / dirs_dev as for rt_cast_rays; tmax_dev: n f32 or NULL (RT_T_MISS); after_dev: n rt_multi_hit records,
+ * 4-byte aligned, of which only t and prim are read — a cursor per ray — or NULL; hits_dev: n x k records, 16-byte
+ * aligned, ray i's record s at index i k + s, exactly 16 n k bytes written; counts_dev: n u32 or NULL. All device memory
+ * on the renderer's GPU; asynchronous on the renderer's stream.
+ *
+ * The answer is stated without a tree (csrc/rt_multihit.hpp is the function, DESIGN.md section 7g the arguments). With rc
+ * the root centre and rr_h the radius bound of the fp16 boxes that the other tree walks use, all in f32 with IEEE
+ * division and square root and an FMA only where written:
+ *   - op = o - rc, D = sqrt(op . op) * 1.001 + rr_h (the dot as (x x + y y) + z z), pad = D * 2^-12,
+ *     inv_k = |d_k| >= 1e-30 ? 1 / d_k : copysign(1e30, d_k), c_lo_k = (-op_k - pad) * inv_k, c_hi_k = (-op_k + pad) * inv_k;
+ *   - slab(box, upper): per axis t0 = fma(lo, inv, c_lo), t1 = fma(hi, inv, c_hi); enter = max(min(t0, t1) over the axes,
+ *     0), exit = min(max(t0, t1) over the axes, upper), minimum and maximum as comparisons; hit when enter <= exit;
+ *   - triangle j's own box: the f64 box of a, a + e1, a + e2 (e1 = b - a, e2 = c - a in f32; -0 as +0) rounded outward
+ *     to f32 with one more ulp, each bound then (float)((double)v - (double)rc_k); a triangle with a non-finite a, e1 or
+ *     e2 has no box;
+ *   - triangle j is accepted when it has a box; the Moller-Trumbore test of rt_cast_rays' tree walk accepts it (the
+ *     same operations in the same order: |det| >= 1e-4, 1 / det the IEEE division, 0 <= u <= 1, v >= 0, u + v <= 1, each
+ *     dot as fma(az, bz, fma(ay, by, ax bx))); 1e-4 <= t_j < cap, where cap follows rt_occluded's tmax rules (NaN and
+ *     everything <= 0: nothing; else min(tmax, RT_T_MISS)); (t_j, j) is lexicographically greater than the cursor's
+ *     (t, prim) when a cursor is given; and slab(box_j, t_j) is hit — the computed t does not lie before the ray enters
+ *     its own triangle's padded box.
+ * Records 0 .. k-1 are the k smallest accepted (t_j, j) in ascending order with the test's own u, v (two triangles at
+ * the same t are both listed, the smaller index first); unused records are the miss record {RT_T_MISS, -1, 0, 0};
+ * counts[i] is the number of all accepted triangles, not capped by k. A ray with a non-finite component of o or d, or
+ * a non-finite D, has no hits and count 0. The spheres of the mixed program do not answer.
+ * Paging: each ray's last record of one call as the next call's cursor yields the next k hits; a miss record as cursor
+ * yields nothing (nothing lies beyond RT_T_MISS), so any number of hits is reachable with k <= RT_MULTI_HIT_MAX_K.
+ * rt_host_cast_rays_multi is that function on the host, and the device returns its bytes on every tree the renderer
+ * holds, with or without counts (without them the walk culls by the list's last t; the records are the same). A query
+ * that overflows the walk's stack of 24 runs the loop over all triangles instead.
+ * Programs and states are rt_closest_points': RT_ERR_ARG in the sphere program, RT_ERR_STATE without a triangle tree
+ * (device geometry or rt_params.tri_bvh = 1; a host SAH tree not built yet is built first). RT_ERR_ARG also for
+ * k > RT_MULTI_HIT_MAX_K (for every n) and, with n > 0, for k = 0 without counts_dev, k > 0 without hits_dev, and a null
+ * or misaligned buffer. n = 0 returns RT_OK and launches nothing, whatever the buffers and the program. It touches no image, frame count, stats, raw counters or learnt cost order. */
+typedef struct rt_multi_hit { float t; int32_t prim; float u, v; } rt_multi_hit;   /* 16 B; miss: RT_T_MISS, -1, 0, 0 */
+#define RT_MULTI_HIT_MAX_K 16u
+int rt_cast_rays_multi(rt_renderer *r, const void *origins_dev, const void *dirs_dev, const void *tmax_dev,
+                       const void *after_dev, uint32_t n, uint32_t k, void *hits_dev, void *counts_dev);
+/* The query on the host: pure CPU, no device; the tree arguments as for rt_host_winding_numbers. node_slots = 0 with a
+ * null hnodes gives the flat definition, a loop over all triangles in index order (order and root_word are not read);
+ * root (centre xyz, radius) is always read: the constants above come from it. origins, dirs: n x 3 f32; tmax: n f32 or
+ * NULL; after16: n records or NULL; hits16: n x k records; counts: n u32 or NULL (k = 0 needs it). RT_ERR_ARG: a null
+ * argument that is needed, k > RT_MULTI_HIT_MAX_K, or bytes that are not a tree over order and the triangles. */
+int rt_host_cast_rays_multi(const void *tris64, uint32_t n_tris, const void *hnodes, size_t node_slots,
+                            const uint32_t *order, size_t n_order, uint32_t root_word, const float root[4],
+                            const float *origins, const float *dirs, const float *tmax, const void *after16,
+                            uint32_t n, uint32_t k, void *hits16, uint32_t *counts);
+
 /* Test-only entry points (fault injection) are declared in hrt_testing.h, not here: they are not part of
  * the drop-in surface. */
 
@@ -706,7 +757,8 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
                              rt_refit_triangles_device / rt_host_lbvh_refit / rt_host_lbvh_cost / rt_get_tri_tree_cost, then
                              rt_set_triangles_device_with / rt_host_lbvh_build_with / rt_host_lbvh_refit_with /
                              rt_get_tri_tree_info, then rt_closest_points / rt_host_closest_points, then rt_winding_numbers /
-                             rt_host_tree_moments / rt_host_winding_numbers, came
+                             rt_host_tree_moments / rt_host_winding_numbers, then rt_cast_rays_multi /
+                             rt_host_cast_rays_multi, came
                              later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 

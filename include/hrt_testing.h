@@ -106,6 +106,15 @@ int rt_testing_get_tree_moments(rt_renderer *r, void *moments_out, size_t moment
 /* Pure CPU: out[i] = csrc/rt_winding.hpp's written-out atan2 of (y[i], x[i]), the function host and device compile. */
 int rt_testing_winding_atan2(const float *y, const float *x, uint32_t n, float *out);
 
+/* on != 0: rt_cast_rays_multi launches the counting instantiation of its kernel (k_cast_rays_multi<., true>: the same walk
+ *   and the same bytes, plus four sums per wave added to four words with one agent-scope atomic each); 0: the product
+ *   kernel, which holds no counting code. Stays set until changed; a new renderer starts with 0. */
+int rt_testing_set_multihit_count(rt_renderer *r, uint32_t on);
+/* Blocking: the four words of the last rt_cast_rays_multi call made with counting on (zeros before the first): {queries,
+ *   triangle tests (all m triangles for a query that ran the loop over all triangles), box tests, queries that overflowed
+ *   the walk's stack}. */
+int rt_testing_get_multihit_counts(rt_renderer *r, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -450,10 +450,9 @@ __device__ __forceinline__ void load_hnode(const uint4* __restrict__ hn, uint32_
 // planes' t values are padded_box_hit's — one FMA per plane, the same roundings — and near <= far without a
 // min / max per axis (min <= max, a bound and its constant order the same way, FMA rounding is monotone; 1/d is never
 // 0 or NaN: robust_inv). One rotate per axis replaces a min and a max: the same visits, bit for bit.
-__device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz, uint32_t shx, uint32_t shy, uint32_t shz,
-                                           const Slab& S, float bt, float& tenter) {
-    const uint32_t x = __builtin_amdgcn_alignbit(px, px, shx), y = __builtin_amdgcn_alignbit(py, py, shy),
-                   z = __builtin_amdgcn_alignbit(pz, pz, shz);
+// box_hit_near: the test on pairs that already hold the near plane in the low half (box_hit_so's after its rotates; the
+// pre-rotated LDS nodes of bvh_walk_noovf<.., PREROT>, read in that order).
+__device__ __forceinline__ bool box_hit_near(uint32_t x, uint32_t y, uint32_t z, const Slab& S, float bt, float& tenter) {
     const float tnx = __builtin_fmaf(h16_lo(x), S.inv.x, S.lo.x), tfx = __builtin_fmaf(h16_hi(x), S.inv.x, S.hi.x);
     const float tny = __builtin_fmaf(h16_lo(y), S.inv.y, S.lo.y), tfy = __builtin_fmaf(h16_hi(y), S.inv.y, S.hi.y);
     const float tnz = __builtin_fmaf(h16_lo(z), S.inv.z, S.lo.z), tfz = __builtin_fmaf(h16_hi(z), S.inv.z, S.hi.z);
@@ -461,6 +460,29 @@ __device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz
     const float tmax = fmin_ieee(fmin_ieee(tfx, tfy), tfz);
     tenter = tmin;
     return tmin <= tmax && tmin <= bt;
+}
+__device__ __forceinline__ bool box_hit_so(uint32_t px, uint32_t py, uint32_t pz, uint32_t shx, uint32_t shy, uint32_t shz,
+                                           const Slab& S, float bt, float& tenter) {
+    const uint32_t x = __builtin_amdgcn_alignbit(px, px, shx), y = __builtin_amdgcn_alignbit(py, py, shy),
+                   z = __builtin_amdgcn_alignbit(pz, pz, shz);
+    return box_hit_near(x, y, z, S, bt, tenter);
+}
+
+// The pre-rotated LDS node table (bvh_walk_noovf<.., PREROT>; k_trace_split's prologue builds it from P.bvh_hnodes): 64 B
+// per node, every [min|max] pair in both orders, so a lane reads the pairs with the near plane in the low half directly —
+// its three choices (the signs of 1/d) are three byte offsets formed once per walk call, where box_hit_so rotates six
+// pairs per box step:
+//   bytes  0..31  x: [c0.x, c1.x, w0, w1] then [rot16(c0.x), rot16(c1.x), w0, w1]   16 B at      (1/d.x < 0 ? 16 : 0)
+//   bytes 32..47  y: [c0.y, c1.y, rot16(c0.y), rot16(c1.y)]                           8 B at 32 + (1/d.y < 0 ?  8 : 0)
+//   bytes 48..63  z: as y                                                             8 B at 48 + (1/d.z < 0 ?  8 : 0)
+// (c0 / c1: the children's words of the fp16 node, w0 / w1 their child words.) 32 B per lane and step, as the 32-B node.
+constexpr uint32_t PREROT_NODE_BYTES = 64u;
+__device__ __forceinline__ void prerot_node(uint4* dst, const uint4 c0, const uint4 c1) {
+    const auto rot = [](uint32_t p) { return __builtin_amdgcn_alignbit(p, p, 16u); };
+    dst[0] = uint4{c0.x, c1.x, c0.w, c1.w};
+    dst[1] = uint4{rot(c0.x), rot(c1.x), c0.w, c1.w};
+    dst[2] = uint4{c0.y, c1.y, rot(c0.y), rot(c1.y)};
+    dst[3] = uint4{c0.z, c1.z, rot(c0.z), rot(c1.z)};
 }
 
 // One sphere of a leaf, at BVH position i: the reference's t, and the (t, slot) minimum kept in (bt, bc).
@@ -513,15 +535,29 @@ __device__ __forceinline__ void leaf_sphere_test(const KParams& P, const Ray& r,
 // SW: the stack's entry type, uint32_t or (k_trace_split<LNODES> without packets: child words sign-extended from 16
 // bits, `hn` holds them so) int16_t: the push stores the low half, the pop sign-extends it back.
 // PAIR (with SELECT; k_trace_split<LNODES> without packets): the leaf's first pass loads two spheres per wait.
+// PREROT (the uncounted k_trace_split<LNODES> of the default schedule): `hn` is the pre-rotated LDS table (prerot_node),
+// and the box step reads its pairs in near / far order at three per-lane addresses: no rotate. Same halves into the same
+// FMAs as box_hit_so: the same visits, bit for bit.
 template <bool SUSPEND, bool SELECT, uint32_t LS, bool COUNT = true, bool HOLD = false, bool PAIR = false,
-          typename SW = uint32_t>
+          typename SW = uint32_t, bool PREROT = false>
 __device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, BvhQuery& Q, SW* stack, Tally& tally,
                                                uint32_t below, const uint4* __restrict__ hn, uint32_t hold = 0u) {
     constexpr bool S16 = sizeof(SW) == 2;
     const Slab S = Q.S;
-    // the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds)
-    const uint32_t shx = (__float_as_uint(S.inv.x) >> 27) & 16u, shy = (__float_as_uint(S.inv.y) >> 27) & 16u,
-                   shz = (__float_as_uint(S.inv.z) >> 27) & 16u;
+    // the rotation of each axis pair, 16 where 1/d < 0 (recomputed per call: not kept across rounds); PREROT: the LDS
+    // byte address of the lane's x, y and z group of node 0 in their place
+    typedef uint32_t w4v __attribute__((ext_vector_type(4)));
+    typedef uint32_t w2v __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(3))) w4v* LdsU4;
+    typedef const __attribute__((address_space(3))) w2v* LdsU2;
+    uint32_t shx = (__float_as_uint(S.inv.x) >> 27) & 16u, shy = (__float_as_uint(S.inv.y) >> 27) & 16u,
+             shz = (__float_as_uint(S.inv.z) >> 27) & 16u;
+    if constexpr (PREROT) {
+        const uint32_t hb = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)hn;
+        shx = hb + shx;
+        shy = hb + 32u + (shy >> 1);
+        shz = hb + 48u + (shz >> 1);
+    }
     const float a = dot(r.d, r.d);  // the same value bvh_begin computed
     const float a4 = 4.0f * a, a2 = 2.0f * a;
     uint32_t node = Q.node;
@@ -571,12 +607,33 @@ __device__ __forceinline__ bool bvh_walk_noovf(const KParams& P, const Ray& r, B
                 }
 #endif
                 float tl, tr;
-                const uint4 c0 = hn[2 * node], c1 = hn[2 * node + 1];
-                const bool hl = box_hit_so(c0.x, c0.y, c0.z, shx, shy, shz, S, bt, tl);
-                const bool hr = box_hit_so(c1.x, c1.y, c1.z, shx, shy, shz, S, bt, tr);
+                bool hl, hr;
+                uint32_t w0, w1;
+                if constexpr (PREROT) {
+                    // (one address per axis: the node's 64 B plus the lane's group base; the x group carries the child words)
+                    // (written as the shift-add instruction: from node * 64 + base the compiler shares the shift and
+                    // adds three times, four instructions for three)
+                    static_assert(PREROT_NODE_BYTES == 64u, "the shift below");
+                    uint32_t ax, ay, az;
+                    asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(ax) : "v"(node), "v"(shx));
+                    asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(ay) : "v"(node), "v"(shy));
+                    asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(az) : "v"(node), "v"(shz));
+                    const w4v gx = *(LdsU4)(uintptr_t)ax;
+                    const w2v gy = *(LdsU2)(uintptr_t)ay, gz = *(LdsU2)(uintptr_t)az;
+                    hl = box_hit_near(gx.x, gy.x, gz.x, S, bt, tl);
+                    hr = box_hit_near(gx.y, gy.y, gz.y, S, bt, tr);
+                    w0 = gx.z;
+                    w1 = gx.w;
+                } else {
+                    const uint4 c0 = hn[2 * node], c1 = hn[2 * node + 1];
+                    hl = box_hit_so(c0.x, c0.y, c0.z, shx, shy, shz, S, bt, tl);
+                    hr = box_hit_so(c1.x, c1.y, c1.z, shx, shy, shz, S, bt, tr);
+                    w0 = c0.w;
+                    w1 = c1.w;
+                }
                 if constexpr (COUNT) tally.boxes += 2;
                 const bool lfirst = hl && (!hr || tl <= tr);
-                const uint32_t near = lfirst ? c0.w : c1.w, far = lfirst ? c1.w : c0.w;
+                const uint32_t near = lfirst ? w0 : w1, far = lfirst ? w1 : w0;
                 const bool both = hl && hr;
                 any = hl || hr;
                 // (the far child is written whether or not it is pushed — one slot past the top when it is
@@ -3318,6 +3375,17 @@ constexpr int split_waves(bool lnodes, bool steal, bool count, bool packet, bool
     if (packet) return steal ? 6 : 7;  // (the stealing packet kernel spills 6 VGPRs at 7 waves)
     return split_stack16(lnodes, packet) && !steal && !count && !ring ? 8 : 7;
 }
+// PREROT (the BLOCKRES kernel: k_trace_split<true, false, false, false>, the default schedule's): the LDS nodes as the
+// pre-rotated 64-B table (prerot_node; bvh_walk_noovf<.., PREROT>), 12 KB where the 32-B nodes take 6. Eight 256-lane
+// workgroups per CU have no room for it (19,968 of their 20,480 B are taken), so the kernel runs in 512-lane workgroups:
+// one copy of the read-only tables serves eight waves, and four workgroups per CU keep 8 waves per SIMD. Per-wave state
+// (the wave's job words, its slice of blk / blk_sky, the stack's lane stride) is indexed by threadIdx.x as before.
+constexpr bool split_prerot(bool lnodes, bool steal, bool count, bool packet, bool ring) {
+    return lnodes && !steal && !count && !packet && !ring;
+}
+constexpr uint32_t split_wg(bool lnodes, bool steal, bool count, bool packet, bool ring) {
+    return split_prerot(lnodes, steal, count, packet, ring) ? 512u : 256u;
+}
 template <bool LNODES, bool STEAL, bool COUNT, bool PACKET, bool RING>
 __device__ __forceinline__ void trace_split(const KParams& P) {
     static_assert(!PACKET || LNODES, "the packet walk reads the LDS nodes and keeps its stack in one VGPR (depth <= 8)");
@@ -3350,14 +3418,26 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     static_assert(!STACK16 || (LNODE_CAP <= 0x8000u && (LNODE_CAP + 1u) * BVH_MAX_LEAF <= 2048u),
                   "a 16-bit stack entry holds a node index or first << 4 | count in 15 bits");
     using StackWord = std::conditional_t<STACK16, int16_t, uint32_t>;
-    __shared__ StackWord bvh_stack[SPLIT_STACK * 256];
-    __shared__ uint4 lnodes[LNODES ? 2 * LNODE_CAP : 1];
+    constexpr bool PREROT = split_prerot(LNODES, STEAL, COUNT, PACKET, RING);
+    constexpr uint32_t WG = split_wg(LNODES, STEAL, COUNT, PACKET, RING);  // the workgroup's lanes
+    static_assert(PREROT == BLOCKRES, "the 512-lane workgroup and the pre-rotated nodes: the BLOCKRES kernel's");
+    __shared__ StackWord bvh_stack[SPLIT_STACK * WG];
+    __shared__ uint4 lnodes[LNODES ? (PREROT ? PREROT_NODE_BYTES / 16u : 2u) * LNODE_CAP : 1];
     // (the packet kernels keep the global large list: their register budget is another; out of this change's scope)
     constexpr bool LLDS = LNODES && !PACKET;
     __shared__ float4 lgeo[LLDS ? LLARGE_CAP : 1];  // the large list's spheres: (cx, cy, cz, r*r), in list order
     if constexpr (LNODES) {
         const uint32_t nn = 2u * min(P.bvh_nnodes, LNODE_CAP);  // renderer.cpp gates LNODES on the same cap
-        for (uint32_t i = threadIdx.x; i < nn; i += 256u) {
+        if constexpr (PREROT) {
+            static_assert(STACK16, "the child words sign-extended, as below");
+            for (uint32_t i = threadIdx.x; 2u * i < nn; i += WG) {  // (a node per lane)
+                uint4 c0 = P.bvh_hnodes[2u * i], c1 = P.bvh_hnodes[2u * i + 1u];
+                c0.w = (uint32_t)(int32_t)(int16_t)(c0.w | (c0.w >> 16));
+                c1.w = (uint32_t)(int32_t)(int16_t)(c1.w | (c1.w >> 16));
+                prerot_node(lnodes + (PREROT_NODE_BYTES / 16u) * i, c0, c1);
+            }
+        } else
+        for (uint32_t i = threadIdx.x; i < nn; i += WG) {
             uint4 c = P.bvh_hnodes[i];
             if constexpr (STACK16) c.w = (uint32_t)(int32_t)(int16_t)(c.w | (c.w >> 16));  // (leaf bit to bit 15, sign-extended)
             lnodes[i] = c;
@@ -3369,9 +3449,9 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
         }
         __syncthreads();
     }
-    __shared__ float4 blk[2 * 256];  // the wave's frame block: (o.xyz, d.x), (d.yz, state bits, ok) per lane
+    __shared__ float4 blk[2 * WG];  // the wave's frame block: (o.xyz, d.x), (d.yz, state bits, ok) per lane
     // SEAMS, a block resolved when it was made (KParams::tile_lists, below): the entry's ninth word, the path's sky_t
-    __shared__ float blk_sky[BLOCKRES ? 256 : 1];
+    __shared__ float blk_sky[BLOCKRES ? WG : 1];
     constexpr uint32_t EW_RES = 0x80000000u;  // entry word of such an entry: 1 | pixel of the tile << 1 | winner's code << 7 | EW_RES
     Tally tally;
     uint32_t queries = 0;
@@ -3400,7 +3480,7 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
     uint32_t nres = 0;   // BLOCKRES: the blocks resolved when made, per wave (a test's observable; HRT_STAMPS: the tallies')
     uint32_t nfull = 0;  // BLOCKRES: the queries left to the full scan, per wave (the uncounted kernels' only sphere tests)
     const auto blk_n = [&]() { return BLOCKRES ? blk_cnt : 64u; };
-    __shared__ uint32_t wjobs[4 * WJ_WORDS];
+    __shared__ uint32_t wjobs[(WG / 64u) * WJ_WORDS];
     // (the fold ring's launches fold nothing of the launch before: renderer.cpp's fold_next needs the sample buffer)
     // (the wave's words, the stack pointer and the lane mask after the fold, whose eight frames in flight take the
     // register budget: nothing of the walk held through it; the packet kernels keep their order, their allocation)
@@ -3719,10 +3799,11 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
             if constexpr (LNODES) {  // (depth <= LNODE_DEPTH = SPLIT_STACK: no overflow)
                 // (the leaf's first pass in pairs: not in the stealing kernels, which spilled 2 VGPRs with it)
                 constexpr bool PAIR = !PACKET && !STEAL;
-                if (bvh_walk_noovf<true, true, 256, COUNT, !PACKET, PAIR>(P, ray, Q, stack, tally, suspend_below, lnodes, hold))
+                if (bvh_walk_noovf<true, true, WG, COUNT, !PACKET, PAIR, StackWord, PREROT>(P, ray, Q, stack, tally, suspend_below,
+                                                                                            lnodes, hold))
                     qs = 2u;
             } else {
-                if (bvh_walk_ovf<true, SPLIT_STACK, true, 256, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))
+                if (bvh_walk_ovf<true, SPLIT_STACK, true, WG, true, COUNT>(P, ray, Q, stack, tally, suspend_below, P.bvh_hnodes))
                     qs = 2u;
             }
         }
@@ -3865,7 +3946,8 @@ __device__ __forceinline__ void trace_split(const KParams& P) {
 }
 // (one kernel per fold mode, as k_trace / k_ring: k_trace_split with the sample buffer, k_ring_split with the fold ring)
 template <bool LNODES, bool STEAL, bool COUNT, bool PACKET>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(split_waves(LNODES, STEAL, COUNT, PACKET, false)))) void
+__global__ __launch_bounds__(split_wg(LNODES, STEAL, COUNT, PACKET, false))
+__attribute__((amdgpu_waves_per_eu(split_waves(LNODES, STEAL, COUNT, PACKET, false)))) void
 k_trace_split(const KParams P) {
     trace_split<LNODES, STEAL, COUNT, PACKET, false>(P);
 }
@@ -4777,7 +4859,8 @@ static hipError_t launch_trace_split(const KParams& P, hipStream_t stream) {
     if (P.steal)
         return P.bvh_lnodes ? launch_persistent(k_trace_split<true, true, COUNT, false>, P, stream, kname_bbbb(base, 1, 1, COUNT, 0))
                             : launch_persistent(k_trace_split<false, true, COUNT, false>, P, stream, kname_bbbb(base, 0, 1, COUNT, 0));
-    return P.bvh_lnodes ? launch_persistent(k_trace_split<true, false, COUNT, false>, P, stream, kname_bbbb(base, 1, 0, COUNT, 0))
+    return P.bvh_lnodes ? launch_persistent(k_trace_split<true, false, COUNT, false>, P, stream, kname_bbbb(base, 1, 0, COUNT, 0),
+                                            split_wg(true, false, COUNT, false, false))
                         : launch_persistent(k_trace_split<false, false, COUNT, false>, P, stream, kname_bbbb(base, 0, 0, COUNT, 0));
 }
 

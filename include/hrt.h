@@ -184,7 +184,9 @@ typedef struct rt_stats {
 } rt_stats;
 
 /* Renderer::new(RenderOutput::Headless(w, h), ..) — renderer.rs:46-269. Zeroes the image (:249-257),
- * frame_count = 0. Selects the program (mode) like include_str!(shader) does (scene_sphere.rs:186). */
+ * frame_count = 0. Selects the program (mode) like include_str!(shader) does (scene_sphere.rs:186).
+ * A width or height of 1 (here or in rt_resize) draws what the reference draws: make_ray divides by W - 1 and H - 1, so
+ * every primary ray and every pixel is NaN, every sample takes exactly one query, and the draw finishes. */
 int rt_create(uint32_t width, uint32_t height, int mode, rt_renderer **out);
 int rt_destroy(rt_renderer *r);
 int rt_get_params(const rt_renderer *r, rt_params *out);

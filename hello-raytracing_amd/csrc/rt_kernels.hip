@@ -1204,9 +1204,14 @@ __device__ __forceinline__ void tri_record(const KParams& P, const Ray& r, const
     h.front = dot(h.n, r.d) > 0.0f;
 }
 
-// The reference's per-leaf update: accept t in [1e-4, best). The walks only track (best, bj); the hit
-// record is built once for the winner (closest_hit), which keeps fewer registers live during the walk.
-template <bool TBUF = false>
+// The reference's per-leaf update, `if t < EPSILON || t >= (*ret).t { return; }` (shader_tris.wgsl:193): a t in
+// [1e-4, best) is accepted, and so is a NaN t (both comparisons are false), after which `best` is NaN and the next
+// triangle with a t that is not below 1e-4 replaces it. A ray with a non-finite component that reaches a triangle
+// (fmin / fmax in the slab test drop a NaN axis) therefore hits with t = NaN, as it does in the oracle's trace().
+// ANY (any_hit): a NaN t is not below tmax, so it is refused and the lane walks on.
+// The walks only track (best, bj); the hit record is built once for the winner (closest_hit), which keeps fewer
+// registers live during the walk.
+template <bool TBUF = false, bool ANY = false>
 __device__ __forceinline__ void tri_test(const KParams& P, const Ray& r, uint32_t j, float& best, int& bj) {
     TriDev tr;
     if constexpr (TBUF) {
@@ -1237,7 +1242,7 @@ __device__ __forceinline__ void tri_test(const KParams& P, const Ray& r, uint32_
     const float v = inv_det * dot(r.d, q);
     if (v < 0.0f || u + v > 1.0f) return;
     const float t = inv_det * dot(e2, q);
-    if (t >= 1e-4f && t < best) {
+    if (ANY ? t >= 1e-4f && t < best : !(t < 1e-4f || t >= best)) {
         best = t;
         bj = (int)j;
     }
@@ -1369,8 +1374,8 @@ __device__ __forceinline__ bool heap_run(const KParams& P, const Ray& r, HeapWal
         for (uint32_t k = 0; k < nc; k++) {  // in the order reached
             const uint32_t e = *(const lds_u32*)(uintptr_t)(c0 + __umul24(k, 4u * LS));
             const uint32_t j = e & ~PAIR_BIT;
-            tri_test<TBUF>(P, r, j, best, bj);
-            if (e & PAIR_BIT) tri_test<TBUF>(P, r, j + 1u, best, bj);
+            tri_test<TBUF, ANY>(P, r, j, best, bj);
+            if (e & PAIR_BIT) tri_test<TBUF, ANY>(P, r, j + 1u, best, bj);
             if constexpr (ANY) {
                 if (bj >= 0) break;
             }
@@ -1419,6 +1424,41 @@ template <bool ANY = false>
 __device__ __forceinline__ void walk_sah(const KParams& /*P*/, const Ray& r, float& best, int& bj, Tally& tally,
                                          uint32_t* stack) {
     const KPtr P = kargs();
+    if constexpr (!ANY) {
+        // A ray with a NaN or infinite component: no box test means anything, and the (t, index) minimum has no place for
+        // the NaN t such a ray gets from a triangle. It is answered as the reference's rule answers it over every triangle
+        // in index order (`t < EPSILON || t >= hit.t` rejects, so a NaN t is accepted and then replaced by the next t not
+        // below 1e-4): what the heap walk gives such a ray when it reaches every leaf. The last triangle with a NaN t
+        // decides where that sequence last restarts, so it is searched from the end (the first triangle tried, for a NaN
+        // in d) and only the triangles after it are run forwards; a ray with no NaN t at all costs every triangle twice.
+        // (any_hit refuses a NaN t and keeps the walk: nothing it could accept lies in a box such a ray misses.)
+        const bool fin = __builtin_isfinite(r.o.x) && __builtin_isfinite(r.o.y) && __builtin_isfinite(r.o.z) &&
+                         __builtin_isfinite(r.d.x) && __builtin_isfinite(r.d.y) && __builtin_isfinite(r.d.z);
+        if (__builtin_expect(!fin, 0)) {
+            const uint32_t m = P->m;
+            uint32_t j = m, tested = 0u;
+            while (j > 0u) {
+                const float t = tri_t(r, P->tris[j - 1u]);
+                tested++;
+                if (t != t) {
+                    best = t;
+                    bj = (int)(j - 1u);
+                    break;
+                }
+                j--;
+            }
+            for (; j < m; j++) {  // (j: one past the last NaN t, or 0)
+                const float t = tri_t(r, P->tris[j]);
+                tested++;
+                if (!(t < 1e-4f || t >= best)) {
+                    best = t;
+                    bj = (int)j;
+                }
+            }
+            tally.tris += tested;
+            return;
+        }
+    }
     const f3 op = mk(r.o.x - P->tb_rc[0], r.o.y - P->tb_rc[1], r.o.z - P->tb_rc[2]);
     const float D = __builtin_amdgcn_sqrtf(dot(op, op)) * 1.001f + P->tb_rr_h;
     const float pad = D * 0x1p-12f;
@@ -1507,8 +1547,8 @@ __device__ __forceinline__ bool closest_hit(const KParams& P, const Ray& r, Hit&
         if constexpr (TSAH) walk_sah(P, r, best, bj, tally, tri_stack);
         else walk_bvh(P, r, best, bj, tally, tri_cand);
     }
-    // every accepted t is < FLT_MAX_REF, so `abs(hit.t - FLT_MAX) < EPSILON` (shader_sphere.wgsl:235) is
-    // "nothing accepted"
+    // every accepted t is < FLT_MAX_REF or, from the reference walk's triangles, NaN, so `abs(hit.t - FLT_MAX) < EPSILON`
+    // (shader_sphere.wgsl:235) is "nothing accepted"
     if (tri_out != nullptr) *tri_out = bj;  // (k_cast_rays: the winning triangle's index; the draws pass none)
     if (bj >= 0) {
         tri_record(P, r, P.tris[bj], best, h);

@@ -186,7 +186,9 @@ typedef struct rt_stats {
 /* Renderer::new(RenderOutput::Headless(w, h), ..) — renderer.rs:46-269. Zeroes the image (:249-257),
  * frame_count = 0. Selects the program (mode) like include_str!(shader) does (scene_sphere.rs:186).
  * A width or height of 1 (here or in rt_resize) draws what the reference draws: make_ray divides by W - 1 and H - 1, so
- * every primary ray and every pixel is NaN, every sample takes exactly one query, and the draw finishes. */
+ * every primary ray and every pixel is NaN, every sample takes exactly one query, and the draw finishes. (With tri_bvh = 1
+ * or a device tree such a ray hits the last triangle with t = NaN at every bounce — the rule for non-finite rays under
+ * rt_cast_rays — so a sample takes rt_params.bounces queries; the pixel is NaN all the same.) */
 int rt_create(uint32_t width, uint32_t height, int mode, rt_renderer **out);
 int rt_destroy(rt_renderer *r);
 int rt_get_params(const rt_renderer *r, rt_params *out);
@@ -372,7 +374,15 @@ typedef struct rt_hit {             /* 32 B */
  *   - sphere program: d is not normalised, so t is in units of |d|; the near root only, t > 0;
  *   - triangle and mixed programs: triangles accept t >= 1e-4, and a triangle replaces a sphere only with a smaller t;
  *   - the reference heap walk keeps its 600-step cap (it may miss what the cap cuts off) unless tri_bvh = 1;
- *   - zero-filled padding slots (rt_params.min_sphere_slots) count as spheres of radius 0 at the origin.
+ *   - zero-filled padding slots (rt_params.min_sphere_slots) count as spheres of radius 0 at the origin;
+ *   - a ray with a non-finite component is answered as trace() answers it. The sphere programs' tests refuse a NaN t. The
+ *     reference heap walk's slab test drops a NaN axis (fmin / fmax) and its triangle test, `t < EPSILON || t >= hit.t`
+ *     rejects, accepts a NaN t, so such a ray can hit with t = NaN, prim the last triangle the walk accepted; a NaN t held
+ *     is replaced by the next t that is not below 1e-4, larger or not. With tri_bvh = 1 and on a device tree the hit of a
+ *     finite ray is the (t, triangle index) minimum over t >= 1e-4; a ray with a NaN or infinite component is answered
+ *     by the reference's rule over every triangle in index order, as if the heap walk reached every leaf: no box is tested
+ *     for it. That costs the triangles after the last one whose t is NaN (none, for a NaN in d) and, for a ray no triangle
+ *     gives a NaN t, every triangle twice.
  * rt_params.variant (0 = auto by slot count), tri_bvh and min_sphere_slots apply as in a tiles draw; the schedule, fold,
  * steal and cost-order knobs do not. n = 0 returns RT_OK and launches nothing; n > 0 with a null pointer is RT_ERR_ARG. A
  * scene state in which a draw fails gives the same status here; no camera is needed. */
@@ -387,7 +397,10 @@ int rt_cast_rays(rt_renderer *r, const void *origins_dev, const void *dirs_dev, 
  * triangle the capped walk never reaches does not occlude), zero padding slots counted as spheres, rt_params.variant /
  * tri_bvh / min_sphere_slots — and a hit at exactly t == tmax does not occlude. A NaN tmax, or any tmax <= 0 including
  * -0, gives 0; a tmax above RT_T_MISS (+inf, FLT_MAX) behaves as RT_T_MISS. Only the values 0 and 1 are ever written,
- * and exactly n bytes are written.
+ * and exactly n bytes are written. A hit with t = NaN (rt_cast_rays, non-finite rays) is not below any tmax and does not
+ * occlude; the walk refuses every NaN t and goes on. One case is therefore answered for the closest finite t instead of
+ * rt_cast_rays' t: a ray for which some triangle tests give a NaN t and others a finite one, where the reference's rule
+ * lets the NaN displace a smaller t it held.
  * A segment query from a to b is o = a, d = b - a, tmax = 1. In the triangle and mixed programs the triangle test's
  * absolute |det| >= 1e-4 makes the result depend on |d| (a short d can fall under it), as it does for rt_cast_rays.
  * The walks start at tmax instead of RT_T_MISS and stop at the first occluder, so a short ray skips most of the scene;
@@ -660,7 +673,7 @@ int rt_host_winding_numbers(const void *tris64, uint32_t n_tris, const void *hno
  * Records 0 .. k-1 are the k smallest accepted (t_j, j) in ascending order with the test's own u, v (two triangles at
  * the same t are both listed, the smaller index first); unused records are the miss record {RT_T_MISS, -1, 0, 0};
  * counts[i] is the number of all accepted triangles, not capped by k. A ray with a non-finite component of o or d, or
- * a non-finite D, has no hits and count 0. The spheres of the mixed program do not answer.
+ * a non-finite D, has no hits and count 0 (rt_cast_rays answers such a ray by the reference's rule instead: see there). The spheres of the mixed program do not answer.
  * Paging: each ray's last record of one call as the next call's cursor yields the next k hits; a miss record as cursor
  * yields nothing (nothing lies beyond RT_T_MISS), so any number of hits is reachable with k <= RT_MULTI_HIT_MAX_K.
  * rt_host_cast_rays_multi is that function on the host, and the device returns its bytes on every tree the renderer

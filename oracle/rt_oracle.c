@@ -144,7 +144,9 @@ static inline v3 rng_vec3(uint32_t *s) {
 }
 
 typedef struct { v3 o, d; } ray_t;
-typedef struct { v3 p, n; float t; const o_material *mat; int front; } hit_t;
+/* prim / tri: the sphere slot or triangle index behind the hit and which of the two it is (the per-ray entry points
+ * report them; trace() does not read them) */
+typedef struct { v3 p, n; float t; const o_material *mat; int front; int prim; int tri; } hit_t;
 
 typedef struct {
     const o_camera *cam; float k;            /* k = tan(fov*0.5) */
@@ -223,7 +225,7 @@ static void closest_sphere(const o_scene *sc, ray_t r, hit_t *h) {
     n = V(divf(n.x, sp->radius), divf(n.y, sp->radius), divf(n.z, sp->radius));
     int front = dot3(r.d, n) < 0.0f;
     if (!front) n = vneg(n);
-    h->p = p; h->n = n; h->t = best; h->mat = &sp->mat; h->front = front;
+    h->p = p; h->n = n; h->t = best; h->mat = &sp->mat; h->front = front; h->prim = idx; h->tri = 0;
 }
 
 /* intersect_node: shader_tris.wgsl:150-159 (inv_d hoisted: identical value for every node) */
@@ -257,6 +259,7 @@ static inline void tri_test(const o_scene *sc, ray_t r, uint32_t j, hit_t *h) {
     h->t = t;
     h->mat = &sc->mats[tr->material];
     h->front = dot3(h->n, r.d) > 0.0f;
+    h->prim = (int)j; h->tri = 1;
 }
 
 /* intersect_all_node: shader_tris.wgsl:268-301 — stackless walk of the implicit heap, 600-step cap */
@@ -338,7 +341,7 @@ static v3 trace(const o_scene *sc, ray_t primary, uint32_t *s, uint64_t *cnt) {
     v3 att = V(1.0f, 1.0f, 1.0f);
     ray_t cur = primary;
     for (uint32_t b = 0; b < sc->bounces; b++) {
-        hit_t h = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, FLT_MAX_REF, 0, 0};
+        hit_t h = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, FLT_MAX_REF, 0, 0, -1, 0};
         if (sc->mode != MODE_TRIS) closest_sphere(sc, cur, &h);
         if (sc->mode != MODE_SPHERE) closest_bvh(sc, cur, &h, cnt);
         cnt[0]++; /* closest-hit queries (rays) */
@@ -353,9 +356,9 @@ static v3 trace(const o_scene *sc, ray_t primary, uint32_t *s, uint64_t *cnt) {
     return vmul(att, sky);
 }
 
-/* fs_main: shader_sphere.wgsl:251-273 — one pixel, one frame */
-static v3 sample_pixel(const o_scene *sc, uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t time,
-                       uint64_t *cnt) {
+/* fs_main up to the trace call: the ray of pixel (x, y) at `time`; *ps is left at the RNG state trace() starts from */
+static ray_t pixel_ray(const o_scene *sc, uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t time,
+                       uint32_t *ps) {
     uint32_t s = (x * H + y) * time;
     float aspect = divf((float)W, (float)H);
     float r1 = rng_float(&s), r2 = rng_float(&s);
@@ -367,8 +370,32 @@ static v3 sample_pixel(const o_scene *sc, uint32_t W, uint32_t H, uint32_t x, ui
     ux = madd(2.0f, ux, -1.0f) * aspect;
     uy = madd(2.0f, uy, -1.0f) * -1.0f;
     ray_t r = make_ray(sc, ux, uy, &s);
+    *ps = s;
+    return r;
+}
+
+/* fs_main: shader_sphere.wgsl:251-273 — one pixel, one frame */
+static v3 sample_pixel(const o_scene *sc, uint32_t W, uint32_t H, uint32_t x, uint32_t y, uint32_t time,
+                       uint64_t *cnt) {
+    uint32_t s;
+    ray_t r = pixel_ray(sc, W, H, x, y, time, &s);
     v3 c = trace(sc, r, &s, cnt);
     return V(0.0f + c.x, 0.0f + c.y, 0.0f + c.z);
+}
+
+/* The scene of one call; the camera may be NULL where no pixel ray is made. */
+static void scene_init(o_scene *sc, const o_params *p, const void *camera80, const void *spheres48, uint32_t nslots,
+                       const uint32_t *sizes, const void *nodes32, const void *tris64, const void *mats32) {
+    sc->cam = (const o_camera *)camera80;
+    sc->k = 0.0f;
+    if (sc->cam)
+        sc->k = OC_TANSC ? sinf(sc->cam->params[2] * 0.5f) * (1.0f / cosf(sc->cam->params[2] * 0.5f)) /* contract 8 */
+                         : tanf(sc->cam->params[2] * 0.5f);
+    sc->spheres = (const o_sphere *)spheres48; sc->nslots = spheres48 ? nslots : 0;
+    sc->nodes = (const o_node *)nodes32; sc->tris = (const o_triangle *)tris64; sc->mats = (const o_material *)mats32;
+    sc->n = sizes ? sizes[0] : 0; sc->m = sizes ? sizes[1] : 0;
+    sc->mode = p->mode; sc->bounces = p->bounces; sc->step_cap = p->step_cap;
+    sc->eps = p->mode == MODE_SPHERE ? 1e-6f : 1e-4f;
 }
 
 /*
@@ -382,14 +409,7 @@ uint64_t oracle_render(const o_params *p, const void *camera80, const void *sphe
                        const uint32_t *sizes, const void *nodes32, const void *tris64, const void *mats32,
                        float *image, int threads, uint64_t *counts) {
     o_scene sc;
-    sc.cam = (const o_camera *)camera80;
-    sc.k = OC_TANSC ? sinf(sc.cam->params[2] * 0.5f) * (1.0f / cosf(sc.cam->params[2] * 0.5f)) /* contract 8 */
-                    : tanf(sc.cam->params[2] * 0.5f);
-    sc.spheres = (const o_sphere *)spheres48; sc.nslots = spheres48 ? nslots : 0;
-    sc.nodes = (const o_node *)nodes32; sc.tris = (const o_triangle *)tris64; sc.mats = (const o_material *)mats32;
-    sc.n = sizes ? sizes[0] : 0; sc.m = sizes ? sizes[1] : 0;
-    sc.mode = p->mode; sc.bounces = p->bounces; sc.step_cap = p->step_cap;
-    sc.eps = p->mode == MODE_SPHERE ? 1e-6f : 1e-4f;
+    scene_init(&sc, p, camera80, spheres48, nslots, sizes, nodes32, tris64, mats32);
     uint64_t total = 0, tnodes = 0, ttris = 0, tcapped = 0;
     /* work items: (row, 64-column chunk) pairs, so a render of a few long rows (the full-frame-count checks of the
        timed configurations: 1-3 rows x 1024-4096 frames) still spreads over every thread; pixels are independent */
@@ -432,6 +452,171 @@ uint64_t oracle_render(const o_params *p, const void *camera80, const void *sphe
     return total;
 }
 
+/* ---- per-ray entry points: the same static functions, asked about a ray instead of a pixel ---- */
+
+/* rt_hit of include/hrt.h, 32 B: the record one bounce of trace() leaves for a ray */
+typedef struct { float t; int32_t prim; float n[3]; uint32_t flags, material, reserved; } o_hit;
+
+/* The closest hit exactly as one iteration of trace() finds it (flat: tri_test over every triangle in index order in
+ * place of the heap walk). Returns trace()'s own hit / miss decision. */
+static int ray_query(const o_scene *sc, ray_t r, int flat, hit_t *h, uint64_t *cnt) {
+    hit_t h0 = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, FLT_MAX_REF, 0, 0, -1, 0};
+    *h = h0;
+    if (sc->mode != MODE_TRIS) closest_sphere(sc, r, h);
+    if (sc->mode != MODE_SPHERE) {
+        if (flat) {
+            for (uint32_t j = 0; j < sc->m; j++) { cnt[2]++; tri_test(sc, r, j, h); }
+        } else {
+            closest_bvh(sc, r, h, cnt);
+        }
+    }
+    cnt[0]++;
+    return !(fabsf(h->t - FLT_MAX_REF) < sc->eps);
+}
+
+static void hit_record(const o_scene *sc, const hit_t *h, int hit, o_hit *out) {
+    memset(out, 0, sizeof *out);
+    out->t = FLT_MAX_REF; out->prim = -1;
+    if (!hit) return;
+    out->t = h->t; out->prim = h->prim;
+    out->n[0] = h->n.x; out->n[1] = h->n.y; out->n[2] = h->n.z;
+    out->flags = (uint32_t)(h->front != 0) | ((uint32_t)(h->tri != 0) << 1);
+    out->material = h->tri ? sc->tris[h->prim].material : (uint32_t)h->prim;
+}
+
+static inline ray_t ld_ray(const float *o, const float *d, int64_t i) {
+    ray_t r; r.o = ld3(o + 3 * i); r.d = ld3(d + 3 * i); return r;
+}
+static inline void st3(float *p, v3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+
+#ifdef _OPENMP
+#define OMP_RAYS(threads) if ((threads) > 0) omp_set_num_threads(threads);
+#else
+#define OMP_RAYS(threads) (void)(threads);
+#endif
+
+/*
+ * oracle_cast_rays: n rays (origins / dirs: n x 3 f32, packed) -> n 32-byte rt_hit records: what one bounce of trace()
+ * sees for each ray. mode, step_cap from p. flat != 0: the triangle part is tri_test over j = 0 .. m-1, no tree.
+ * counts (may be NULL): {rays, node tests, triangle tests, walks cut by the cap}. Returns the rays that hit.
+ */
+uint64_t oracle_cast_rays(const o_params *p, const void *spheres48, uint32_t nslots, const uint32_t *sizes,
+                          const void *nodes32, const void *tris64, const void *mats32, uint32_t n,
+                          const float *origins, const float *dirs, int flat, void *hits32, int threads,
+                          uint64_t *counts) {
+    o_scene sc;
+    scene_init(&sc, p, 0, spheres48, nslots, sizes, nodes32, tris64, mats32);
+    o_hit *out = (o_hit *)hits32;
+    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, nhit = 0;
+    OMP_RAYS(threads)
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : c0, c1, c2, c3, nhit)
+#endif
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        uint64_t q[4] = {0, 0, 0, 0};
+        hit_t h;
+        int hit = ray_query(&sc, ld_ray(origins, dirs, i), flat, &h, q);
+        hit_record(&sc, &h, hit, &out[i]);
+        c0 += q[0]; c1 += q[1]; c2 += q[2]; c3 += q[3]; nhit += (uint64_t)hit;
+    }
+    if (counts) { counts[0] = c0; counts[1] = c1; counts[2] = c2; counts[3] = c3; }
+    return nhit;
+}
+
+/*
+ * oracle_trace_rays: n rays -> 0.0f + trace(ray) (radiance: n x 3 f32) and the closest-hit queries of each path
+ * (queries: n u32, may be NULL). rng: the n states trace() starts from, or NULL = s_i = (i + 1) * seed in u32.
+ * bounces, mode, step_cap from p. Returns the total queries; counts as oracle_cast_rays.
+ */
+uint64_t oracle_trace_rays(const o_params *p, const void *spheres48, uint32_t nslots, const uint32_t *sizes,
+                           const void *nodes32, const void *tris64, const void *mats32, uint32_t n,
+                           const float *origins, const float *dirs, const uint32_t *rng, uint32_t seed,
+                           float *radiance, uint32_t *queries, int threads, uint64_t *counts) {
+    o_scene sc;
+    scene_init(&sc, p, 0, spheres48, nslots, sizes, nodes32, tris64, mats32);
+    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    OMP_RAYS(threads)
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : c0, c1, c2, c3)
+#endif
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        uint64_t q[4] = {0, 0, 0, 0};
+        uint32_t s = rng ? rng[i] : ((uint32_t)i + 1u) * seed;
+        v3 c = trace(&sc, ld_ray(origins, dirs, i), &s, q);
+        st3(radiance + 3 * i, V(0.0f + c.x, 0.0f + c.y, 0.0f + c.z));
+        if (queries) queries[i] = (uint32_t)q[0];
+        c0 += q[0]; c1 += q[1]; c2 += q[2]; c3 += q[3];
+    }
+    if (counts) { counts[0] = c0; counts[1] = c1; counts[2] = c2; counts[3] = c3; }
+    return c0;
+}
+
+/*
+ * oracle_bounce_step: one iteration of trace()'s loop on state the caller holds: origins, dirs (n x 3 f32), rng (n u32)
+ * and throughput (n x 3 f32, may be NULL). A ray that hits gets the scattered ray, the advanced state and
+ * throughput * (albedo * 0.7); a ray that misses has nothing touched. Every ray: hits32[i] (may be NULL) is the record of
+ * the ray before the scatter and hit_flags[i] (may be NULL) is 1 for a hit. p->bounces is not read. Returns the hits.
+ */
+uint64_t oracle_bounce_step(const o_params *p, const void *spheres48, uint32_t nslots, const uint32_t *sizes,
+                            const void *nodes32, const void *tris64, const void *mats32, uint32_t n, float *origins,
+                            float *dirs, uint32_t *rng, float *throughput, void *hits32, uint8_t *hit_flags,
+                            int threads, uint64_t *counts) {
+    o_scene sc;
+    scene_init(&sc, p, 0, spheres48, nslots, sizes, nodes32, tris64, mats32);
+    o_hit *out = (o_hit *)hits32;
+    uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, nhit = 0;
+    OMP_RAYS(threads)
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : c0, c1, c2, c3, nhit)
+#endif
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        uint64_t q[4] = {0, 0, 0, 0};
+        hit_t h;
+        ray_t cur = ld_ray(origins, dirs, i);
+        int hit = ray_query(&sc, cur, 0, &h, q);
+        if (out) hit_record(&sc, &h, hit, &out[i]);
+        if (hit_flags) hit_flags[i] = (uint8_t)hit;
+        if (hit) {
+            uint32_t s = rng[i];
+            cur = scatter(&sc, &s, cur, &h);
+            rng[i] = s;
+            st3(origins + 3 * i, cur.o);
+            st3(dirs + 3 * i, cur.d);
+            if (throughput) {
+                const float *al = h.mat->albedo;
+                v3 att = vmul(ld3(throughput + 3 * i), V(al[0] * 0.7f, al[1] * 0.7f, al[2] * 0.7f));
+                st3(throughput + 3 * i, att);
+            }
+        }
+        c0 += q[0]; c1 += q[1]; c2 += q[2]; c3 += q[3]; nhit += (uint64_t)hit;
+    }
+    if (counts) { counts[0] = c0; counts[1] = c1; counts[2] = c2; counts[3] = c3; }
+    return nhit;
+}
+
+/*
+ * oracle_primary_rays: for the pixels p selects (rows and columns as oracle_render, same layout k * nx + (x - x0)) and one
+ * `time`, the ray sample_pixel hands to trace() (origins / dirs: 3 f32 each) and the RNG state after make_ray (rng, may
+ * be NULL). Only width, height, mode and the pixel window of p are read.
+ */
+void oracle_primary_rays(const o_params *p, const void *camera80, uint32_t time, float *origins, float *dirs,
+                         uint32_t *rng) {
+    o_scene sc;
+    scene_init(&sc, p, camera80, 0, 0, 0, 0, 0, 0);
+    const uint32_t rb = p->row_block > 1 ? p->row_block : 1;
+    for (uint32_t k = 0; k < p->nrows; k++) {
+        uint32_t y = p->row0 + (k / rb) * p->row_step * rb + k % rb;
+        for (uint32_t x = p->x0; x < p->x0 + p->nx; x++) {
+            size_t i = (size_t)k * p->nx + (x - p->x0);
+            uint32_t s;
+            ray_t r = pixel_ray(&sc, p->width, p->height, x, y, time, &s);
+            st3(origins + 3 * i, r.o);
+            st3(dirs + 3 * i, r.d);
+            if (rng) rng[i] = s;
+        }
+    }
+}
+
 /* Size checks so the ctypes wrapper can verify it agrees on the POD layouts. */
 uint32_t oracle_sizeof(int which) {
     switch (which) {
@@ -441,6 +626,7 @@ uint32_t oracle_sizeof(int which) {
     case 3: return sizeof(o_node);
     case 4: return sizeof(o_triangle);
     case 5: return sizeof(o_params);
+    case 6: return sizeof(o_hit);
     default: return 0;
     }
 }

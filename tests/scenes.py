@@ -257,6 +257,36 @@ def oracle_render(sd: SceneDef, **kw):
     return O.render(**args)
 
 
+def _oracle_ray_args(sd: SceneDef, kw: dict) -> dict:
+    args = dict(mode=sd.mode, spheres=sd.spheres, bvh=sd.bvh, min_sphere_slots=sd.min_sphere_slots)
+    args.update(kw)
+    return args
+
+
+def oracle_cast_rays(sd: SceneDef, origins, dirs, **kw):
+    """oracle.cast_rays on a SceneDef: (HIT_DTYPE records, counts)."""
+    from oracle import oracle as O
+    return O.cast_rays(origins, dirs, **_oracle_ray_args(sd, kw))
+
+
+def oracle_trace_rays(sd: SceneDef, origins, dirs, **kw):
+    """oracle.trace_rays on a SceneDef with its bounce cap: (radiance, queries, counts)."""
+    from oracle import oracle as O
+    return O.trace_rays(origins, dirs, **_oracle_ray_args(sd, dict(bounces=sd.bounces, **kw)))
+
+
+def oracle_bounce_step(sd: SceneDef, origins, dirs, rng, throughput, **kw):
+    """oracle.bounce_step on a SceneDef: (origins, dirs, rng, throughput, records, hit flags)."""
+    from oracle import oracle as O
+    return O.bounce_step(origins, dirs, rng, throughput, **_oracle_ray_args(sd, kw))
+
+
+def oracle_primary_rays(sd: SceneDef, time: int, **kw):
+    """oracle.primary_rays on a SceneDef: (origins, dirs (rows, nx, 3), rng (rows, nx))."""
+    from oracle import oracle as O
+    return O.primary_rays(width=sd.width, height=sd.height, mode=sd.mode, camera=sd.camera, time=time, **kw)
+
+
 # ---- committed oracle fixtures (tests/golden/oracle, made by tests/golden/make_oracle_fixtures.py)
 ORACLE_FIXTURE_DIR = GOLDEN_DIR / "oracle"
 

@@ -26,6 +26,7 @@
 #include "rt_lbvh.hpp"
 #include "rt_regroup.hpp"
 #include "rt_multihit.hpp"
+#include "rt_overlap.hpp"
 #include "rt_winding.hpp"
 #include "rt_tile_lists.hpp"
 
@@ -51,6 +52,7 @@ hipError_t hrt_launch_closest(const hrt_closest::Launch& a, bool count, hipStrea
 hipError_t hrt_launch_winding(const hrt_winding::Launch& a, bool count, hipStream_t stream);      // rt_winding.hip
 hipError_t hrt_launch_tree_moments(const hrt_winding::MomentsLaunch& a, hipStream_t stream);      // rt_winding.hip
 hipError_t hrt_launch_multihit(const hrt_multihit::Launch& a, bool stats, hipStream_t stream);    // rt_multihit.hip
+hipError_t hrt_launch_overlap(const hrt_overlap::Launch& a, bool stats, hipStream_t stream);      // rt_overlap.hip
 hipError_t hrt_launch_trace(int mode, int variant, const hrt_dev::KParams& P, hipStream_t stream);
 hipError_t hrt_launch_order(uint32_t* pixel_cost, uint32_t ntiles, uint32_t* tile_sum, uint32_t* order, uint32_t* scratch,
                             hipStream_t stream);
@@ -277,6 +279,9 @@ struct rt_renderer {
     // rt_cast_rays_multi's counting instantiation (hrt_testing.h): selected by multihit_count, its four words
     DevBuf<unsigned long long> multihit_counts;
     bool multihit_count = false;
+    // rt_overlap_volumes' counting instantiation (hrt_testing.h): selected by overlap_count, its four words
+    DevBuf<unsigned long long> overlap_counts;
+    bool overlap_count = false;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -306,7 +311,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + multihit_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + multihit_counts.bytes() + overlap_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -1205,6 +1210,7 @@ void delete_buffers(rt_renderer* r) {
     r->closest_counts.release();
     r->winding_counts.release();
     r->multihit_counts.release();
+    r->overlap_counts.release();
     r->tb_moments.release();
     r->moments_dirty = true;
     r->tile_lists_valid = false;
@@ -2430,6 +2436,108 @@ int rt_testing_get_multihit_counts(rt_renderer* r, uint64_t out[4]) {
     DeviceScope ds(r->device);
     if (ds.rc) return ds.rc;
     HIP_TRY(hipMemcpyAsync(out, r->multihit_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+// ---- volume queries (include/hrt.h; rt_overlap.hip k_overlap, rt_overlap.hpp the function) ----
+int rt_overlap_volumes(rt_renderer* r, uint32_t kind, const void* volumes_dev, const void* after_dev, uint32_t n, uint32_t k,
+                       void* hits_dev, void* counts_dev) {
+    if (!r) return fail(RT_ERR_ARG, "rt_overlap_volumes: null");
+    if (k > RT_OVERLAP_MAX_K) return fail(RT_ERR_ARG, "rt_overlap_volumes: k exceeds RT_OVERLAP_MAX_K");
+    if (kind != RT_VOLUME_BOX && kind != RT_VOLUME_BALL) return fail(RT_ERR_ARG, "rt_overlap_volumes: unknown kind");
+    if (n == 0) return RT_OK;
+    if (k == 0 && !counts_dev) return fail(RT_ERR_ARG, "rt_overlap_volumes: k = 0 needs counts");
+    if (k > 0 && !hits_dev) return fail(RT_ERR_ARG, "rt_overlap_volumes: k > 0 needs hits");
+    if (!volumes_dev) return fail(RT_ERR_ARG, "rt_overlap_volumes: null buffer");
+    if (misaligned(16, {hits_dev}) || misaligned(4, {volumes_dev, after_dev, counts_dev}))
+        return fail(RT_ERR_ARG, "rt_overlap_volumes: hits must be 16-byte aligned, every other buffer 4-byte aligned");
+    static_assert(sizeof(rt_overlap_hit) == 16, "rt_overlap_hit: one 16-byte store per record (k_overlap)");
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_overlap_volumes: the sphere program has no triangle tree");
+    if (!r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, "rt_overlap_volumes: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    if (q.rc) return q.rc;
+    hrt_overlap::Launch a{};
+    a.tree.hnodes = (const hrt_overlap::U4*)q.P.tb_hnodes;
+    a.tree.order = q.P.tb_order;
+    a.tree.geo = q.P.tri_geo;
+    a.tree.m = q.P.m;
+    a.tree.root = q.P.tb_root;
+    a.tree.flat = 0u;
+    for (int c = 0; c < 3; c++) a.tree.rc[c] = q.P.tb_rc[c];
+    a.tree.rr_h = q.P.tb_rr_h;
+    a.volumes = (const float*)volumes_dev;
+    a.after = (const hrt_overlap::Hit*)after_dev;
+    a.hits = hits_dev;
+    a.counts = (uint32_t*)counts_dev;
+    a.n = n;
+    a.k = k;
+    a.kind = kind;
+    if (r->overlap_count) {
+        if (int rc = ensure(r->overlap_counts, 4)) return rc;
+        HIP_TRY(hipMemsetAsync(r->overlap_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
+        a.stats = r->overlap_counts.ptr;
+    }
+    HIP_TRY(hrt_launch_overlap(a, r->overlap_count, r->stream));
+    return RT_OK;
+}
+
+// The query on the host (rt_overlap.hpp host_overlap): pure CPU, no device; the bytes the device writes for that tree.
+int rt_host_overlap_volumes(const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots, const uint32_t* order,
+                            size_t n_order, uint32_t root_word, const float root[4], uint32_t kind, const float* volumes,
+                            const void* after16, uint32_t n, uint32_t k, void* hits16, uint32_t* counts) {
+    const char* const who = "rt_host_overlap_volumes";
+    if (k > RT_OVERLAP_MAX_K) return fail(RT_ERR_ARG, std::string(who) + ": k exceeds RT_OVERLAP_MAX_K");
+    if (kind != RT_VOLUME_BOX && kind != RT_VOLUME_BALL) return fail(RT_ERR_ARG, std::string(who) + ": unknown kind");
+    if (n && k == 0 && !counts) return fail(RT_ERR_ARG, std::string(who) + ": k = 0 needs counts");
+    if (n && (!volumes || (k && !hits16))) return fail(RT_ERR_ARG, std::string(who) + ": null volumes or hits");
+    if (n_tris && !tris64) return fail(RT_ERR_ARG, std::string(who) + ": null triangles");
+    if (!root) return fail(RT_ERR_ARG, std::string(who) + ": null root");
+    if ((node_slots != 0) != (hnodes != nullptr)) return fail(RT_ERR_ARG, std::string(who) + ": nodes and node_slots disagree");
+    if (node_slots && n_order && !order) return fail(RT_ERR_ARG, std::string(who) + ": null order");
+    if (node_slots >= (1u << 26) || n_order > (1u << 26))
+        return fail(RT_ERR_ARG, std::string(who) + ": 2^26 or more node slots or positions");
+    std::vector<float> aee;
+    aee_of_triangles(tris64, n_tris, aee);
+    std::vector<hrt_overlap::U4> nodes(2 * node_slots);  // copied: no alignment asked of the caller
+    if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
+    std::vector<uint32_t> ord;
+    if (node_slots && n_order) ord.assign(order, order + n_order);
+    hrt_overlap::Tree T{};
+    T.hnodes = nodes.data();
+    T.order = ord.data();
+    T.geo = aee.data();
+    T.m = n_tris;
+    T.root = root_word;
+    T.flat = node_slots ? 0u : 1u;
+    for (int c = 0; c < 3; c++) T.rc[c] = root[c];
+    T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
+    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, ord.size()))
+        return fail(RT_ERR_ARG, std::string(who) + ": the nodes are not a tree over order and the triangles");
+    std::vector<hrt_overlap::Hit> after, out((size_t)n * k);
+    if (after16 && n) {
+        after.resize(n);
+        std::memcpy(after.data(), after16, (size_t)n * sizeof(hrt_overlap::Hit));
+    }
+    hrt_overlap::host_overlap(T, kind, volumes, after16 ? after.data() : nullptr, n, k, out.data(), counts);
+    if (!out.empty()) std::memcpy(hits16, out.data(), out.size() * sizeof(hrt_overlap::Hit));
+    return RT_OK;
+}
+
+int rt_testing_set_overlap_count(rt_renderer* r, uint32_t on) {
+    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_overlap_count: null");
+    r->overlap_count = on != 0u;
+    return RT_OK;
+}
+
+int rt_testing_get_overlap_counts(rt_renderer* r, uint64_t out[4]) {
+    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_overlap_counts: null");
+    for (int c = 0; c < 4; c++) out[c] = 0;
+    if (!r->overlap_counts.ptr) return RT_OK;
+    DeviceScope ds(r->device);
+    if (ds.rc) return ds.rc;
+    HIP_TRY(hipMemcpyAsync(out, r->overlap_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }

@@ -6,11 +6,11 @@ package is the host-side mirror of the reference's Rust scene API plus ctypes pl
 from . import _lib
 from ._lib import (REGROUP_CELL_OCTANT, REGROUP_KEYS, REGROUP_TILE, RtRegroup, RT_HIT_FRONT, RT_HIT_TRIANGLE, RT_T_MISS, UGUARD_COLUMNS, UGUARD_HELPERS, LIB_PATH, RT_FOLD_AUTO, RT_FOLD_BUFFER, RT_FOLD_NEXT, RT_FOLD_RING, RT_MODE_MIXED, RT_SCHEDULE_AUTO, RT_SCHEDULE_QUEUE, RT_SCHEDULE_TILES, RT_MODE_SPHERE, RT_MODE_TRIS, RtError, RtParams, RtStats,
                    lib)
-from .scene import (CAMERA_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, MULTI_HIT_DTYPE, MULTI_HIT_MAX_K, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
+from .scene import (CAMERA_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, MULTI_HIT_DTYPE, MULTI_HIT_MAX_K, OVERLAP_HIT_DTYPE, OVERLAP_MAX_K, VOLUME_BOX, VOLUME_BALL, DIELECTRIC, LAMBERTIAN, MATERIAL_DTYPE, MAX_OBJECT_IN_SCENE, METAL,
                     NODE_DTYPE, PI, SPHERE_DTYPE, TRIANGLE_DTYPE, Camera, ComparisonError, Material, Mesh, OrbitCamera,
                     Renderer, SceneSphere, SceneTris, Sphere, Tree, Vec3, compare_ppm_images, f32,
                     closest_points_host, lbvh_build, lbvh_cost, lbvh_refit, ppm_from_image, read_asset, render_ppm, spheres_array,
-                    tree_moments_host, winding_numbers_host, cast_rays_multi_host)
+                    tree_moments_host, winding_numbers_host, cast_rays_multi_host, overlap_volumes_host)
 
 
 def device_count() -> int:
@@ -107,4 +107,5 @@ __all__ = [
     "lbvh_build", "lbvh_refit", "lbvh_cost", "CLOSEST_DTYPE", "closest_points_host",
     "tree_moments_host", "winding_numbers_host",
     "MULTI_HIT_DTYPE", "MULTI_HIT_MAX_K", "cast_rays_multi_host",
+    "OVERLAP_HIT_DTYPE", "OVERLAP_MAX_K", "VOLUME_BOX", "VOLUME_BALL", "overlap_volumes_host",
 ]

@@ -181,6 +181,9 @@ SIGNATURES = {
     "rt_cast_rays_multi": (C.c_int, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P]),
     "rt_host_cast_rays_multi": (C.c_int, [_P, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _U32, _PF, _PF, _PF, _PF, _P, _U32,
                                           _U32, _P, _PU32]),
+    "rt_overlap_volumes": (C.c_int, [_P, _U32, _P, _P, _U32, _U32, _P, _P]),
+    "rt_host_overlap_volumes": (C.c_int, [_P, _U32, _P, C.c_size_t, _PU32, C.c_size_t, _U32, _PF, _U32, _PF, _P, _U32, _U32, _P,
+                                          _PU32]),
     "rt_primary_rng": (C.c_int, [_P, _U32, _P, C.c_size_t]),
     "rt_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "rt_read_image": (C.c_int, [_P, _PF, C.c_size_t]),
@@ -242,6 +245,8 @@ TESTING_SIGNATURES = {
     "rt_testing_get_winding_counts": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rt_testing_set_multihit_count": (C.c_int, [_P, _U32]),
     "rt_testing_get_multihit_counts": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "rt_testing_set_overlap_count": (C.c_int, [_P, _U32]),
+    "rt_testing_get_overlap_counts": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rt_testing_get_tree_moments": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rt_testing_winding_atan2": (C.c_int, [_PF, _PF, _U32, _PF]),
 }

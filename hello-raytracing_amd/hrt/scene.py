@@ -54,6 +54,12 @@ assert CLOSEST_DTYPE.itemsize == 32
 MULTI_HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("u", "<f4"), ("v", "<f4")])
 MULTI_HIT_MAX_K = 16
 assert MULTI_HIT_DTYPE.itemsize == 16
+# rt_overlap_hit (include/hrt.h): one record of rt_overlap_volumes; the kinds of volume and their floats per query
+OVERLAP_HIT_DTYPE = np.dtype([("d2", "<f4"), ("prim", "<i4"), ("v", "<f4"), ("w", "<f4")])
+OVERLAP_MAX_K = 16
+VOLUME_BOX, VOLUME_BALL = 1, 2
+_VOLUME_FLOATS = {VOLUME_BOX: 6, VOLUME_BALL: 4}
+assert OVERLAP_HIT_DTYPE.itemsize == 16
 assert CAMERA_DTYPE.itemsize == 80 and MATERIAL_DTYPE.itemsize == 32 and SPHERE_DTYPE.itemsize == 48
 assert NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 64
 
@@ -775,6 +781,145 @@ class Renderer:
         check(lib().rt_testing_get_multihit_counts(self._h, c), "testing_get_multihit_counts")
         return np.array(list(c), dtype=np.uint64)
 
+    def overlap_records(self, kind: int, volumes, k: int, after=None, counts: bool = False):
+        """rt_overlap_volumes, the raw records: an (N, k, 4) int32 tensor on the renderer's device, one 16-byte
+        rt_overlap_hit per query and rank (OVERLAP_HIT_DTYPE on the host), and the (N,) int32 counts or None. kind:
+        VOLUME_BOX (volumes (N, 6) float32: lo xyz, hi xyz) or VOLUME_BALL ((N, 4) float32: centre xyz, squared radius),
+        a torch tensor on the renderer's device or a numpy array; after: None, or the cursors as an (N, 4) int32 tensor on
+        the renderer's device (one record per query, e.g. records[:, -1]) or N OVERLAP_HIT_DTYPE numpy records.
+        Synchronises torch's current stream before the call and the renderer after it."""
+        import torch
+
+        who = "overlap_volumes"
+        if kind not in _VOLUME_FLOATS:
+            raise ValueError(f"{who}: kind must be VOLUME_BOX or VOLUME_BALL, got {kind}")
+        width = _VOLUME_FLOATS[kind]
+        dev = self._torch_device()
+        vol = volumes
+        if not torch.is_tensor(vol):
+            vol = np.asarray(vol)
+            if vol.dtype != np.float32:
+                raise ValueError(f"{who}: volumes must be float32, got {vol.dtype}")
+            vol = torch.from_numpy(np.ascontiguousarray(vol)).to(dev)
+        if vol.dtype != torch.float32 or vol.dim() != 2 or vol.shape[1] != width:
+            raise ValueError(f"{who}: volumes must be (N, {width}) float32, got {tuple(vol.shape)} {vol.dtype}")
+        if vol.device != dev:
+            raise ValueError(f"{who}: volumes are on {vol.device}, the renderer draws on {dev}")
+        vol = vol.contiguous()
+        n = int(vol.shape[0])
+        if n >= 1 << 32:
+            raise ValueError(f"{who}: at most 2^32 - 1 queries per call")
+        k = int(k)
+        if not 0 <= k <= OVERLAP_MAX_K:
+            raise ValueError(f"{who}: k must be 0 .. {OVERLAP_MAX_K}, got {k}")
+        if k == 0 and not counts:
+            raise ValueError(f"{who}: k = 0 needs counts = True")
+        cur = after
+        if cur is not None:
+            if not torch.is_tensor(cur):
+                cur = np.ascontiguousarray(cur, dtype=OVERLAP_HIT_DTYPE).reshape(-1)
+                cur = torch.from_numpy(cur.view(np.int32).reshape(-1, 4)).to(dev)
+            if cur.dtype != torch.int32 or tuple(cur.shape) != (n, 4):
+                raise ValueError(f"{who}: after must be ({n}, 4) int32 records, got {tuple(cur.shape)} {cur.dtype}")
+            if cur.device != dev:
+                raise ValueError(f"{who}: after is on {cur.device}, the renderer draws on {dev}")
+            cur = cur.contiguous()
+        hits = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
+        cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
+        self._query(who, lib().rt_overlap_volumes, kind, _ptr(vol), _ptr(cur), n, k, _ptr(hits) if k else None, _ptr(cnt))
+        return hits, cnt
+
+    def _overlap_dict(self, rec, cnt, counts: bool) -> dict:
+        import torch
+
+        f = rec.view(torch.float32)
+        out = {"d2": f[:, :, 0].clone(), "prim": rec[:, :, 1].clone(), "v": f[:, :, 2].clone(), "w": f[:, :, 3].clone(),
+               "records": rec}
+        if counts:
+            out["count"] = cnt
+        return out
+
+    def overlap_boxes(self, lo, hi, k: int, after=None, counts: bool = False) -> dict:
+        """rt_overlap_volumes, RT_VOLUME_BOX: the triangles that touch each axis-aligned box [lo, hi] (touching counts),
+        the k of smallest index, in index order, on the renderer's triangle tree (triangle and mixed programs, with device
+        geometry or tri_bvh = 1; the spheres of the mixed program do not answer). lo, hi: (N, 3) float32, torch tensors on
+        the renderer's device or numpy arrays; k: 0 .. 16; after: a cursor per box, see overlap_records. Returns torch
+        tensors on the renderer's device: prim (N, k) int32 (-1 for an unused rank), d2 (N, k) float32 (0 for a hit,
+        RT_T_MISS for an unused rank), v, w (N, k) float32 (0), records (N, k, 4) int32 (the raw records), and with
+        counts = True count (N,) int32, the number of all such triangles beyond the cursor, not capped by k."""
+        import torch
+
+        lo_t = self._rays_on_device("overlap_boxes", lo, "lo")
+        hi_t = self._rays_on_device("overlap_boxes", hi, "hi")
+        if lo_t.shape != hi_t.shape:
+            raise ValueError(f"overlap_boxes: {tuple(lo_t.shape)} lo for {tuple(hi_t.shape)} hi")
+        rec, cnt = self.overlap_records(VOLUME_BOX, torch.cat([lo_t, hi_t], dim=1), k, after, counts)
+        return self._overlap_dict(rec, cnt, counts)
+
+    def nearest_triangles(self, points, k: int, max_dist2=None, after=None, counts: bool = False) -> dict:
+        """rt_overlap_volumes, RT_VOLUME_BALL: the k nearest triangles of each point, in (d2, prim) order, on the
+        renderer's triangle tree. points: (N, 3) float32; max_dist2 as closest_points (None: however far; a triangle at
+        exactly max_dist2 does not count); after: a cursor per point, see overlap_records. Returns torch tensors on the
+        renderer's device: d2 (N, k) float32 (RT_T_MISS for an unused rank), prim (N, k) int32 (-1 there), v, w (N, k)
+        float32 (the weights of the triangle's b and c at its nearest point), records (N, k, 4) int32, and with counts =
+        True count (N,) int32, the number of all triangles nearer than max_dist2 and beyond the cursor."""
+        import torch
+
+        who = "nearest_triangles"
+        pts = self._rays_on_device(who, points, "points")
+        n = int(pts.shape[0])
+        cap = self._per_ray_f32(who, "max_dist2", max_dist2, n)
+        if cap is None:
+            cap = torch.full((n,), _lib.RT_T_MISS, dtype=torch.float32, device=pts.device)
+        rec, cnt = self.overlap_records(VOLUME_BALL, torch.cat([pts, cap[:, None]], dim=1), k, after, counts)
+        return self._overlap_dict(rec, cnt, counts)
+
+    def all_overlaps(self, kind: int, volumes):
+        """Every triangle of every volume, ragged: one counting call (k = 0), then pages of 16 by cursor over the queries
+        that still have triangles left. Returns (offsets, d2, prim, v, w) on the renderer's device: offsets (N + 1,)
+        int64, query i's triangles at [offsets[i], offsets[i + 1]) of d2 (float32), prim (int32), v, w (float32), in index
+        order (boxes) or (d2, prim) order (balls)."""
+        import torch
+
+        dev = self._torch_device()
+        vol = volumes if torch.is_tensor(volumes) else torch.from_numpy(np.ascontiguousarray(volumes)).to(dev)
+        _, cnt = self.overlap_records(kind, vol, 0, None, True)
+        n = int(vol.shape[0])
+        cnt = cnt.to(torch.int64)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=offsets[1:])
+        total = int(offsets[-1].item()) if n else 0
+        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        rows = torch.nonzero(cnt > 0).reshape(-1)
+        done = torch.zeros((n,), dtype=torch.int64, device=dev)
+        cursor = None
+        K = OVERLAP_MAX_K
+        rank = torch.arange(K, device=dev, dtype=torch.int64)
+        while rows.numel():
+            rec, _ = self.overlap_records(kind, vol[rows], K, cursor, False)
+            left = (cnt[rows] - done[rows]).clamp(max=K)
+            take = rank[None, :] < left[:, None]
+            dst = (offsets[rows] + done[rows])[:, None] + rank[None, :]
+            out[dst[take]] = rec[take]
+            done[rows] += left
+            more = done[rows] < cnt[rows]
+            cursor = rec[more][:, K - 1, :].contiguous()
+            rows = rows[more]
+        f = out.view(torch.float32)
+        return offsets, f[:, 0].clone(), out[:, 1].clone(), f[:, 2].clone(), f[:, 3].clone()
+
+    def set_overlap_count(self, on: bool) -> None:
+        """Test-only: overlap_records runs the counting instantiation of its kernel (include/hrt_testing.h
+        rt_testing_set_overlap_count)."""
+        check(lib().rt_testing_set_overlap_count(self._h, 1 if on else 0), "testing_set_overlap_count")
+
+    def overlap_counts(self) -> np.ndarray:
+        """Test-only: uint64[4] of the last counted overlap_records call: queries, triangle tests, box tests, stack
+        overflows (include/hrt_testing.h rt_testing_get_overlap_counts)."""
+        c = (C.c_uint64 * 4)()
+        check(lib().rt_testing_get_overlap_counts(self._h, c), "testing_get_overlap_counts")
+        return np.array(list(c), dtype=np.uint64)
+
     def winding_numbers(self, points, beta: float = 0.0):
         """rt_winding_numbers: the generalized winding number of the renderer's triangles at each point (triangle and
         mixed programs, with device geometry or tri_bvh = 1; the spheres of the mixed program do not answer): 1 inside a
@@ -1230,6 +1375,35 @@ def cast_rays_multi_host(triangles: np.ndarray, tree: dict, origins: np.ndarray,
                                         hits.ctypes.data if hits.size else None,
                                         cnt.ctypes.data_as(_lib._PU32) if cnt is not None else None),
           "rt_host_cast_rays_multi")
+    return (hits, cnt) if counts else hits
+
+
+def overlap_volumes_host(triangles: np.ndarray, tree: dict, kind: int, volumes: np.ndarray, k: int, after=None,
+                         counts: bool = False, flat: bool = False):
+    """rt_host_overlap_volumes (include/hrt.h): Renderer.overlap_records on the host, no device, for the tree dict `tree`
+    (lbvh_build / lbvh_refit / Renderer.tri_tree): the bytes the device writes for that tree. flat = True runs the flat
+    definition instead, a loop over all triangles in index order; only the tree's root (centre, radius) is read then.
+    kind: VOLUME_BOX (volumes (n, 6) float32) or VOLUME_BALL ((n, 4) float32); after: None or n OVERLAP_HIT_DTYPE records
+    (d2 and prim are read). Returns (n, k) OVERLAP_HIT_DTYPE records, and with counts = True a pair of them and (n,)
+    uint32 counts (k = 0 needs counts)."""
+    keep, args = _winding_tree_args(triangles, tree)
+    if flat:
+        args = args[:2] + (None, 0, None, 0, 0x80000000) + args[7:]
+    width = _VOLUME_FLOATS.get(kind, 1)
+    vol = np.ascontiguousarray(volumes, dtype=np.float32).reshape(-1, width)
+    n = len(vol)
+    cur = None
+    if after is not None:
+        cur = np.ascontiguousarray(after, dtype=OVERLAP_HIT_DTYPE)
+        if cur.shape != (n,):
+            raise ValueError(f"overlap_volumes_host: after must be ({n},) records, got {cur.shape}")
+    hits = np.zeros((n, k), dtype=OVERLAP_HIT_DTYPE)
+    cnt = np.zeros((n,), dtype=np.uint32) if counts else None
+    check(lib().rt_host_overlap_volumes(*args, kind, vol.ctypes.data_as(_lib._PF) if n else None,
+                                        cur.ctypes.data if cur is not None and n else None, n, k,
+                                        hits.ctypes.data if hits.size else None,
+                                        cnt.ctypes.data_as(_lib._PU32) if cnt is not None else None),
+          "rt_host_overlap_volumes")
     return (hits, cnt) if counts else hits
 
 

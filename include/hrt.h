@@ -697,6 +697,61 @@ int rt_host_cast_rays_multi(const void *tris64, uint32_t n_tris, const void *hno
                             const float *origins, const float *dirs, const float *tmax, const void *after16,
                             uint32_t n, uint32_t k, void *hits16, uint32_t *counts);
 
+/* Volume queries (no reference counterpart): the triangles that touch an axis-aligned box, or the k nearest triangles of
+ * a point within a radius, in order, and the number of all of them — the collision broad and narrow phase, voxelising a
+ * mesh, neighbourhoods of a point, which one rt_closest_points record per point cannot give. Triangle and mixed programs,
+ * on the triangle tree rt_closest_points walks. kind: RT_VOLUME_BOX or RT_VOLUME_BALL; volumes_dev: n queries packed as
+ * the kind says, 4-byte aligned; after_dev: n rt_overlap_hit records, 4-byte aligned, of which only d2 and prim are read —
+ * a cursor per query — or NULL; hits_dev: n x k records, 16-byte aligned, query i's record s at index i k + s, exactly
+ * 16 n k bytes written; counts_dev: n u32 or NULL. All device memory on the renderer's GPU; asynchronous on the
+ * renderer's stream.
+ *
+ * The answer is stated without a tree (csrc/rt_overlap.hpp is the function, DESIGN.md section 7h the arguments), over the
+ * triangle records (a, e1 = b - a, e2 = c - a in f32) in index order, all in f32, every operation rounded once in the
+ * order written, no FMA, with rc the root centre:
+ *   - box (lo, hi): nothing for a non-finite bound or lo_k > hi_k on an axis. q_lo_k = the f32 at or below
+ *     (double)lo_k - (double)rc_k, one more ulp down, q_hi_k likewise up; c_k = 0.5f lo_k + 0.5f hi_k,
+ *     h_k = 0.5f hi_k - 0.5f lo_k; per triangle v0 = a - c, v1 = v0 + e1, v2 = v0 + e2, f0 = e1, f1 = e2 - e1, f2 = -e2.
+ *     Triangle j is accepted when it has a box box_j (rt_cast_rays_multi's: none for a non-finite a, e1 or e2);
+ *     q_lo_k <= box_j.hi_k && box_j.lo_k <= q_hi_k on all three axes; none of the nine axes unit_k x f_i separates — with
+ *     k1 = (k + 1) % 3, k2 = (k + 2) % 3, a1 = -f_i[k2], a2 = f_i[k1]: p_m = a1 v_m[k1] + a2 v_m[k2] per vertex,
+ *     r = h[k1] |a1| + h[k2] |a2|, separating when min(p) > r or max(p) < -r; and the plane axis n = e1 x e2 (each
+ *     component as a product less a product) does not separate, with p_m = (n_x v_m.x + n_y v_m.y) + n_z v_m.z and
+ *     r = (h_x |n_x| + h_y |n_y|) + h_z |n_z|. A comparison that fails, also one a NaN fails, does not separate: touching
+ *     overlaps, and a degenerate triangle answers as the segment or point it is. Records {0.0f, j, 0, 0}, ascending in j.
+ *   - ball (c, r2): cap follows rt_closest_points' maxd2 rules (NaN and everything <= 0: nothing; else min(r2,
+ *     RT_T_MISS)); (d2_j, v, w) is rt_closest_points' point-triangle function of c and triangle j; accepted when
+ *     d2_j < cap (equality does not count). Records {d2_j, j, v, w}, ascending in (d2, j). A non-finite c has no hits.
+ *   - with a cursor a triangle is accepted only when (d2_j, j) — (0.0f, j) in the box kind — is lexicographically greater
+ *     than the cursor's (d2, prim).
+ * Records 0 .. k-1 are the first k accepted in that order; unused records are the miss record {RT_T_MISS, -1, 0, 0};
+ * counts[i] is the number of all accepted triangles, not capped by k; a smaller k is a prefix of a larger one. The spheres
+ * of the mixed program do not answer. Paging: each query's last record of one call as the next call's cursor yields the
+ * next k; a miss record as cursor yields nothing.
+ * rt_host_overlap_volumes is that function on the host, and the device returns its bytes on every tree the renderer holds,
+ * with or without counts. A ball whose D = |c - rc| * 1.001 + rr_h lies outside [2^-40, 2^60], and a query that overflows
+ * the walk's stack of 24, runs the loop over all triangles instead.
+ * Programs and states are rt_cast_rays_multi's: RT_ERR_ARG in the sphere program, RT_ERR_STATE without a triangle tree
+ * (device geometry or rt_params.tri_bvh = 1; a host SAH tree not built yet is built first). RT_ERR_ARG also for
+ * k > RT_OVERLAP_MAX_K and for an unknown kind (for every n) and, with n > 0, for k = 0 without counts_dev, k > 0 without
+ * hits_dev, and a null or misaligned buffer. n = 0 returns RT_OK and launches nothing, whatever the buffers and the
+ * program. It touches no image, frame count, stats, raw counters or learnt cost order. */
+#define RT_VOLUME_BOX   1u   /* volumes: n x 6 f32  {lo.x lo.y lo.z hi.x hi.y hi.z}              */
+#define RT_VOLUME_BALL  2u   /* volumes: n x 4 f32  {c.x c.y c.z r2}  r2 = squared radius (a cap) */
+#define RT_OVERLAP_MAX_K 16u
+typedef struct rt_overlap_hit { float d2; int32_t prim; float v, w; } rt_overlap_hit;  /* 16 B; miss: RT_T_MISS, -1, 0, 0 */
+int rt_overlap_volumes(rt_renderer *r, uint32_t kind, const void *volumes_dev, const void *after_dev,
+                       uint32_t n, uint32_t k, void *hits_dev, void *counts_dev);
+/* The query on the host: pure CPU, no device; the tree arguments as for rt_host_cast_rays_multi. node_slots = 0 with a
+ * null hnodes gives the flat definition, a loop over all triangles in index order (order and root_word are not read);
+ * root (centre xyz, radius) is always read. volumes: n x 6 or n x 4 f32; after16: n records or NULL; hits16: n x k
+ * records; counts: n u32 or NULL (k = 0 needs it). RT_ERR_ARG: a null argument that is needed, k > RT_OVERLAP_MAX_K, an
+ * unknown kind, or bytes that are not a tree over order and the triangles. */
+int rt_host_overlap_volumes(const void *tris64, uint32_t n_tris, const void *hnodes, size_t node_slots,
+                            const uint32_t *order, size_t n_order, uint32_t root_word, const float root[4],
+                            uint32_t kind, const float *volumes, const void *after16,
+                            uint32_t n, uint32_t k, void *hits16, uint32_t *counts);
+
 /* Test-only entry points (fault injection) are declared in hrt_testing.h, not here: they are not part of
  * the drop-in surface. */
 
@@ -773,7 +828,7 @@ int rt_get_device(const rt_renderer *r, int32_t *ordinal, int32_t pci[3]);
                              rt_set_triangles_device_with / rt_host_lbvh_build_with / rt_host_lbvh_refit_with /
                              rt_get_tri_tree_info, then rt_closest_points / rt_host_closest_points, then rt_winding_numbers /
                              rt_host_tree_moments / rt_host_winding_numbers, then rt_cast_rays_multi /
-                             rt_host_cast_rays_multi, came
+                             rt_host_cast_rays_multi, then rt_overlap_volumes / rt_host_overlap_volumes, came
                              later without a new version (no struct changed): detect them by their symbols */
 int rt_abi_version(uint32_t *version, uint32_t *params_bytes, uint32_t *stats_bytes);
 

@@ -115,6 +115,15 @@ int rt_testing_set_multihit_count(rt_renderer *r, uint32_t on);
  *   the walk's stack}. */
 int rt_testing_get_multihit_counts(rt_renderer *r, uint64_t out[4]);
 
+/* on != 0: rt_overlap_volumes launches the counting instantiation of its kernel (k_overlap<., ., true>: the same walk and
+ *   the same bytes, plus four sums per wave added to four words with one agent-scope atomic each); 0: the product
+ *   kernel, which holds no counting code. Stays set until changed; a new renderer starts with 0. */
+int rt_testing_set_overlap_count(rt_renderer *r, uint32_t on);
+/* Blocking: the four words of the last rt_overlap_volumes call made with counting on (zeros before the first): {queries,
+ *   triangle tests (all m triangles for a query that ran the loop over all triangles), box tests, queries that overflowed
+ *   the walk's stack}. */
+int rt_testing_get_overlap_counts(rt_renderer *r, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

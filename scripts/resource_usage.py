@@ -1,4 +1,4 @@
-"""Compiler resource usage of every product kernel of the seven device translation units (rt_kernels.hip, rt_regroup.hip, rt_lbvh.hip, rt_ploc.hip, rt_closest.hip, rt_winding.hip, rt_multihit.hip) (VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy), from
+"""Compiler resource usage of every product kernel of the eight device translation units (rt_kernels.hip, rt_regroup.hip, rt_lbvh.hip, rt_ploc.hip, rt_closest.hip, rt_winding.hip, rt_multihit.hip, rt_overlap.hip) (VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy), from
 hipcc -Rpass-analysis=kernel-resource-usage with the product flags (hello-raytracing_amd/Makefile).
 
 usage: python scripts/resource_usage.py [extra hipcc flags ...] > profiles/rNN/resource_usage.txt
@@ -17,11 +17,11 @@ KEYS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("VGPRs Sp
 
 
 def main() -> int:
-    # one translation unit after the other: rt_kernels.hip's rows first, as before; then rt_regroup.hip's, rt_lbvh.hip's, rt_ploc.hip's, rt_closest.hip's, rt_winding.hip's and rt_multihit.hip's
+    # one translation unit after the other: rt_kernels.hip's rows first, as before; then rt_regroup.hip's, rt_lbvh.hip's, rt_ploc.hip's, rt_closest.hip's, rt_winding.hip's, rt_multihit.hip's and rt_overlap.hip's
     csrc = ROOT / "hello-raytracing_amd" / "csrc"
     out, cmds = "", []
     for src in (csrc / "rt_kernels.hip", csrc / "rt_regroup.hip", csrc / "rt_lbvh.hip", csrc / "rt_ploc.hip",
-                csrc / "rt_closest.hip", csrc / "rt_winding.hip", csrc / "rt_multihit.hip"):
+                csrc / "rt_closest.hip", csrc / "rt_winding.hip", csrc / "rt_multihit.hip", csrc / "rt_overlap.hip"):
         cmd = ["/opt/rocm/bin/hipcc", *FLAGS, *sys.argv[1:], str(src), "-o", "/tmp/hrt_ru.o",
                "-Rpass-analysis=kernel-resource-usage"]
         out += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr

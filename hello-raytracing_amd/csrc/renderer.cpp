@@ -125,9 +125,11 @@ int ensure_within(DevBuf<T>& b, size_t n, size_t budget, size_t fail_above) {
 // Makes `device` current for one rt_* call and restores the caller's device after it: a renderer's memory, stream
 // and launches stay on the GPU it was created on whatever device the calling thread has current (one process
 // driving several GPUs, or a caller that switches devices between calls).
+// prior: the status of a check made before it; when that failed nothing is done and rc is that status.
 struct DeviceScope {
-    int prev = -1, rc = RT_OK;
-    explicit DeviceScope(int device) {
+    int prev = -1, rc;
+    explicit DeviceScope(int device, int prior = RT_OK) : rc(prior) {
+        if (rc) return;
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess) {
             rc = fail(RT_ERR_DEVICE, "hipGetDevice failed");
@@ -145,6 +147,32 @@ struct DeviceScope {
     }
     DeviceScope(const DeviceScope&) = delete;
     DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
+// The counter words of one tree query's counting instantiation (include/hrt_testing.h): `on` selects it, the first
+// counted call allocates the words.
+struct CounterSlot {
+    DevBuf<unsigned long long> buf;
+    bool on = false;
+    // Before a launch: *words = the `n` words, zeroed on `stream`, or null when counting is off.
+    int arm(size_t n, hipStream_t stream, unsigned long long** words) {
+        *words = nullptr;
+        if (!on) return RT_OK;
+        if (int rc = ensure(buf, n)) return rc;
+        HIP_TRY(hipMemsetAsync(buf.ptr, 0, n * sizeof(unsigned long long), stream));
+        *words = buf.ptr;
+        return RT_OK;
+    }
+    // The `n` words of the last counted call (zeros before the first one). Blocking.
+    int read(int device, hipStream_t stream, uint64_t* out, size_t n) const {
+        std::fill(out, out + n, uint64_t{0});
+        if (!buf.ptr) return RT_OK;
+        DeviceScope ds(device);
+        if (ds.rc) return ds.rc;
+        HIP_TRY(hipMemcpyAsync(out, buf.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
 };
 
 int check_device(int* dev_out) {
@@ -267,21 +295,13 @@ struct rt_renderer {
     size_t wave_trace_words = 0;
     // rt_regroup_paths' sort: 4 u32 per entry, and the digit counts (rt_regroup.hpp Launch; include/hrt.h has the size rule)
     DevBuf<uint32_t> regroup_entries, regroup_counts;
-    // rt_closest_points' counting instantiation (hrt_testing.h): selected by closest_count, its four words
-    DevBuf<unsigned long long> closest_counts;
-    bool closest_count = false;
+    // the counting instantiations of rt_closest_points (4 words), rt_winding_numbers (5), rt_cast_rays_multi (4) and
+    // rt_overlap_volumes (4) (hrt_testing.h)
+    CounterSlot closest_count, winding_count, multihit_count, overlap_count;
     // rt_winding_numbers: the moments of the tree in tb_hnodes (rt_winding.hpp: 16 floats per node slot), made by the first
-    // call after anything that changed the tree (moments_dirty); its counting instantiation's five words (hrt_testing.h)
+    // call after anything that changed the tree (moments_dirty)
     DevBuf<float> tb_moments;
     bool moments_dirty = true;
-    DevBuf<unsigned long long> winding_counts;
-    bool winding_count = false;
-    // rt_cast_rays_multi's counting instantiation (hrt_testing.h): selected by multihit_count, its four words
-    DevBuf<unsigned long long> multihit_counts;
-    bool multihit_count = false;
-    // rt_overlap_volumes' counting instantiation (hrt_testing.h): selected by overlap_count, its four words
-    DevBuf<unsigned long long> overlap_counts;
-    bool overlap_count = false;
 
     // host copy of the spheres (slot arrays are rebuilt when min_sphere_slots changes)
     std::vector<hrt::Sphere> spheres;
@@ -311,7 +331,7 @@ struct rt_renderer {
                tri_geo.bytes() + mats.bytes() +
                tb_hnodes.bytes() + tb_order.bytes() + tb_parent.bytes() + counter.bytes() + count_spread.bytes() + samples.bytes() + samples2.bytes() + ring.bytes() + ring_ctl.bytes() +
                wave_trace.bytes() + steal_slots.bytes() + queues.bytes() + tile_cost.bytes() + tile_sum.bytes() + tile_order.bytes() +
-               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_counts.bytes() + tb_moments.bytes() + winding_counts.bytes() + multihit_counts.bytes() + overlap_counts.bytes() + lb_tris.bytes() + lb_geo.bytes() +
+               order_scratch.bytes() + tile_lists.bytes() + regroup_entries.bytes() + regroup_counts.bytes() + closest_count.buf.bytes() + tb_moments.bytes() + winding_count.buf.bytes() + multihit_count.buf.bytes() + overlap_count.buf.bytes() + lb_tris.bytes() + lb_geo.bytes() +
                lb_mats.bytes() + lb_hnodes.bytes() + lb_order.bytes() + lb_keys.bytes() + lb_parent.bytes() +
                lb_arrivals.bytes() + lb_boxes.bytes() + lb_stat.bytes();
     }
@@ -1207,10 +1227,7 @@ void delete_buffers(rt_renderer* r) {
     r->tile_sum.release();
     r->tile_order.release();
     r->tile_lists.release();
-    r->closest_counts.release();
-    r->winding_counts.release();
-    r->multihit_counts.release();
-    r->overlap_counts.release();
+    for (CounterSlot* c : {&r->closest_count, &r->winding_count, &r->multihit_count, &r->overlap_count}) c->buf.release();
     r->tb_moments.release();
     r->moments_dirty = true;
     r->tile_lists_valid = false;
@@ -1225,17 +1242,42 @@ bool misaligned(size_t align, std::initializer_list<const void*> ptrs) {
     return false;
 }
 
+// The refusals of a call that reads the triangle tree. any_tree: a tree the call itself has built when there is none (the
+// read-outs of the tree), so only the sphere program is refused.
+int need_tri_tree(const rt_renderer* r, const char* who, bool any_tree = false) {
+    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, std::string(who) + ": the sphere program has no triangle tree");
+    if (!any_tree && !r->dev_geom && !r->params.tri_bvh)
+        return fail(RT_ERR_STATE, std::string(who) + ": no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    return RT_OK;
+}
+
 // What every ray query sets up once its arguments are checked, in this order: the renderer's device made current, the
-// scene's kernel arguments (scene_params) and the scan variant a tiles draw would run. rc: the first failure.
+// scene's kernel arguments (scene_params) and the scan variant a tiles draw would run. rc: the first failure. A query on
+// the triangle tree names itself in tree_who: need_tri_tree's refusals come first then, and scene_params has uploaded the
+// tree (upload_tri_tree builds a host SAH tree that is not built yet).
 struct QueryScope {
     DeviceScope ds;
     hrt_dev::KParams P{};
     int variant = hrt_dev::SCAN_SIMPLE, rc;
-    explicit QueryScope(rt_renderer* r) : ds(r->device), rc(ds.rc) {
+    explicit QueryScope(rt_renderer* r, const char* tree_who = nullptr)
+        : ds(r->device, tree_who ? need_tri_tree(r, tree_who) : RT_OK), rc(ds.rc) {
         if (!rc) rc = scene_params(r, P);
         if (!rc && r->mode != RT_MODE_TRIS) variant = resolve_variant(r);
     }
 };
+
+// The tree fields of a tree query's launch arguments (rt_closest.hpp Launch itself; the Tree of the other three), from the
+// scene's kernel arguments.
+template <typename T>
+void tree_fields(T& t, const hrt_dev::KParams& P) {
+    t.hnodes = (const hrt_lbvh::U4*)P.tb_hnodes;
+    t.order = P.tb_order;
+    t.geo = P.tri_geo;
+    t.m = P.m;
+    t.root = P.tb_root;
+    for (int k = 0; k < 3; k++) t.rc[k] = P.tb_rc[k];
+    t.rr_h = P.tb_rr_h;
+}
 
 }  // namespace
 
@@ -1748,7 +1790,7 @@ int rt_host_lbvh_cost(const void* hnodes, size_t node_slots, uint32_t root_word,
 // the status block's cost words, which no draw reads.
 int rt_get_tri_tree_cost(rt_renderer* r, uint64_t cost[4]) {
     if (!r || !cost) return fail(RT_ERR_ARG, "rt_get_tri_tree_cost: null");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_get_tri_tree_cost: the sphere program has no triangle tree");
+    if (int rc = need_tri_tree(r, "rt_get_tri_tree_cost", true)) return rc;
     DeviceScope ds(r->device);
     if (ds.rc) return ds.rc;
     if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
@@ -1768,9 +1810,7 @@ int rt_get_tri_tree_cost(rt_renderer* r, uint64_t cost[4]) {
 // What the renderer walks, in numbers (include/hrt.h). A host SAH tree not built yet is built first.
 int rt_get_tri_tree_info(rt_renderer* r, uint32_t info[8]) {
     if (!r || !info) return fail(RT_ERR_ARG, "rt_get_tri_tree_info: null");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_get_tri_tree_info: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_get_tri_tree_info: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    if (int rc = need_tri_tree(r, "rt_get_tri_tree_info")) return rc;
     DeviceScope ds(r->device);
     if (ds.rc) return ds.rc;
     if (int rc = upload_tri_tree(r)) return rc;
@@ -1784,7 +1824,7 @@ int rt_get_tri_tree_info(rt_renderer* r, uint32_t info[8]) {
 int rt_testing_get_tri_tree(rt_renderer* r, void* hnodes_out, size_t hnode_cap, uint32_t* order_out, size_t order_cap,
                             uint32_t info[8], float root[4]) {
     if (!r || !info || !root) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: null");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_testing_get_tri_tree: the sphere program has no triangle tree");
+    if (int rc = need_tri_tree(r, "rt_testing_get_tri_tree", true)) return rc;
     DeviceScope ds(r->device);
     if (ds.rc) return ds.rc;
     if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
@@ -2083,29 +2123,16 @@ int rt_closest_points(rt_renderer* r, const void* points_dev, const void* maxd2_
     if (misaligned(16, {out_dev}) || misaligned(4, {points_dev, maxd2_dev}))
         return fail(RT_ERR_ARG, "rt_closest_points: out must be 16-byte aligned, points and maxd2 4-byte aligned");
     static_assert(sizeof(rt_closest) == 32, "rt_closest: two 16-byte stores per record (k_closest_points)");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_closest_points: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_closest_points: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
-    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    QueryScope q(r, "rt_closest_points");
     if (q.rc) return q.rc;
     hrt_closest::Launch a{};
-    a.hnodes = (const hrt_closest::U4*)q.P.tb_hnodes;
-    a.order = q.P.tb_order;
-    a.geo = q.P.tri_geo;
-    a.m = q.P.m;
-    a.root = q.P.tb_root;
-    for (int k = 0; k < 3; k++) a.rc[k] = q.P.tb_rc[k];
-    a.rr_h = q.P.tb_rr_h;
+    tree_fields(a, q.P);
     a.points = (const float*)points_dev;
     a.maxd2 = (const float*)maxd2_dev;
     a.out = out_dev;
     a.n = n;
-    if (r->closest_count) {
-        if (int rc = ensure(r->closest_counts, 4)) return rc;
-        HIP_TRY(hipMemsetAsync(r->closest_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
-        a.counts = r->closest_counts.ptr;
-    }
-    HIP_TRY(hrt_launch_closest(a, r->closest_count, r->stream));
+    if (int rc = r->closest_count.arm(4, r->stream, &a.counts)) return rc;
+    HIP_TRY(hrt_launch_closest(a, r->closest_count.on, r->stream));
     return RT_OK;
 }
 
@@ -2114,35 +2141,48 @@ int rt_host_closest_points(const void* tris64, uint32_t n_tris, const float* poi
                            void* out32) {
     if (n_tris && !tris64) return fail(RT_ERR_ARG, "rt_host_closest_points: null triangles");
     if (n && (!points || !out32)) return fail(RT_ERR_ARG, "rt_host_closest_points: null points or out");
-    std::vector<float> aee(9 * (size_t)n_tris);
-    for (uint32_t j = 0; j < n_tris; j++) {
-        hrt::Triangle t;  // (no alignment asked of the caller)
-        std::memcpy(&t, (const char*)tris64 + 64u * (size_t)j, sizeof t);
-        const float v[9] = {t.a.x, t.a.y, t.a.z, t.b.x - t.a.x, t.b.y - t.a.y, t.b.z - t.a.z,
-                            t.c.x - t.a.x, t.c.y - t.a.y, t.c.z - t.a.z};
-        std::copy(v, v + 9, &aee[9 * (size_t)j]);
-    }
+    std::vector<float> aee;
+    aee_of_triangles(tris64, n_tris, aee);
     std::vector<hrt_closest::Record> out(n);
     hrt_closest::host_closest(aee.data(), n_tris, points, maxd2, n, out.data());
     if (n) std::memcpy(out32, out.data(), (size_t)n * sizeof(hrt_closest::Record));
     return RT_OK;
 }
 
-int rt_testing_set_closest_count(rt_renderer* r, uint32_t on) {
-    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_closest_count: null");
-    r->closest_count = on != 0u;
+// The counting instantiations' switches and read-outs (include/hrt_testing.h), one CounterSlot each.
+static int set_counting(rt_renderer* r, CounterSlot rt_renderer::*slot, uint32_t on, const char* who) {
+    if (!r) return fail(RT_ERR_ARG, std::string(who) + ": null");
+    (r->*slot).on = on != 0u;
     return RT_OK;
 }
+static int get_counts(rt_renderer* r, CounterSlot rt_renderer::*slot, uint64_t* out, size_t words, const char* who) {
+    if (!r || !out) return fail(RT_ERR_ARG, std::string(who) + ": null");
+    return (r->*slot).read(r->device, r->stream, out, words);
+}
 
+int rt_testing_set_closest_count(rt_renderer* r, uint32_t on) {
+    return set_counting(r, &rt_renderer::closest_count, on, "rt_testing_set_closest_count");
+}
 int rt_testing_get_closest_counts(rt_renderer* r, uint64_t out[4]) {
-    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_closest_counts: null");
-    for (int k = 0; k < 4; k++) out[k] = 0;
-    if (!r->closest_counts.ptr) return RT_OK;
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    HIP_TRY(hipMemcpyAsync(out, r->closest_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return RT_OK;
+    return get_counts(r, &rt_renderer::closest_count, out, 4, "rt_testing_get_closest_counts");
+}
+int rt_testing_set_winding_count(rt_renderer* r, uint32_t on) {
+    return set_counting(r, &rt_renderer::winding_count, on, "rt_testing_set_winding_count");
+}
+int rt_testing_get_winding_counts(rt_renderer* r, uint64_t out[5]) {
+    return get_counts(r, &rt_renderer::winding_count, out, 5, "rt_testing_get_winding_counts");
+}
+int rt_testing_set_multihit_count(rt_renderer* r, uint32_t on) {
+    return set_counting(r, &rt_renderer::multihit_count, on, "rt_testing_set_multihit_count");
+}
+int rt_testing_get_multihit_counts(rt_renderer* r, uint64_t out[4]) {
+    return get_counts(r, &rt_renderer::multihit_count, out, 4, "rt_testing_get_multihit_counts");
+}
+int rt_testing_set_overlap_count(rt_renderer* r, uint32_t on) {
+    return set_counting(r, &rt_renderer::overlap_count, on, "rt_testing_set_overlap_count");
+}
+int rt_testing_get_overlap_counts(rt_renderer* r, uint64_t out[4]) {
+    return get_counts(r, &rt_renderer::overlap_count, out, 4, "rt_testing_get_overlap_counts");
 }
 
 // ---- winding numbers (include/hrt.h; rt_winding.hip k_winding / k_tree_moments, rt_winding.hpp the function) ----
@@ -2167,7 +2207,7 @@ int ensure_moments(rt_renderer* r) {
         if (!rc) rc = ensure(r->lb_boxes, 2 * (size_t)slots * hrt_winding::SUM_WORDS);
         if (rc) return rc;
         hrt_winding::MomentsLaunch a{};
-        a.hnodes = (const hrt_winding::U4*)r->tb_hnodes.ptr;
+        a.hnodes = (const hrt_lbvh::U4*)r->tb_hnodes.ptr;
         a.order = r->tb_order.ptr;
         a.geo = r->tri_geo.ptr;
         a.parent = r->tb_parent.ptr;
@@ -2180,7 +2220,7 @@ int ensure_moments(rt_renderer* r) {
     } else {
         const std::vector<uint4> hpacked = pack_bvh_hnodes(r->tri_tree.nodes, r->tri_tree.root_center);
         hrt_winding::Tree T{};
-        T.hnodes = (const hrt_winding::U4*)hpacked.data();
+        T.hnodes = (const hrt_lbvh::U4*)hpacked.data();
         T.order = r->tri_tree.order.data();
         T.geo = r->tri_aee.data();
         T.m = (uint32_t)(r->tri_aee.size() / 9);
@@ -2195,40 +2235,63 @@ int ensure_moments(rt_renderer* r) {
     r->moments_dirty = false;
     return RT_OK;
 }
+}  // namespace
 
-// The host mirrors' tree argument, copied (no alignment asked of the caller) and checked as far as a size can be.
-struct HostWindingTree {
+}  // extern "C" (HostTree has a template member)
+
+namespace {
+// The tree argument of the host mirrors (rt_host_tree_moments, rt_host_winding_numbers, rt_host_cast_rays_multi,
+// rt_host_overlap_volumes), copied (no alignment asked of the caller) and checked as far as a size can be; whether the
+// nodes are a tree is the caller's to judge (host_moments, host_tree_ok). The mirrors do not refuse the same calls, and
+// each keeps its rules:
+//   strict   (multi-hit, volumes) the root is always read and the root word passed on; nodes and node_slots must agree;
+//            order is read only with nodes.
+//   lenient  (winding) without nodes nothing of the tree is read, not even the root: the root word is LEAF_BIT; order is
+//            copied whenever it is given; a root word past node_slots is refused here.
+struct HostTree {
     std::vector<float> aee;
-    std::vector<hrt_winding::U4> nodes;
+    std::vector<hrt_lbvh::U4> nodes;
     std::vector<uint32_t> ord;
-    hrt_winding::Tree T{};
+    uint32_t m = 0, root_word = hrt_lbvh::LEAF_BIT;
+    float rc3[3] = {0.0f, 0.0f, 0.0f}, rr_h = 0.0f;
     int rc = RT_OK;
-    HostWindingTree(const char* who, const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots,
-                    const uint32_t* order, size_t n_order, uint32_t root_word, const float root[4]) {
+    HostTree(const char* who, bool strict, const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots,
+             const uint32_t* order, size_t n_order, uint32_t word, const float root[4]) {
         const std::string w(who);
         if (n_tris && !tris64) rc = fail(RT_ERR_ARG, w + ": null triangles");
-        else if (node_slots && (!hnodes || !root)) rc = fail(RT_ERR_ARG, w + ": null nodes or root");
-        else if (n_order && !order) rc = fail(RT_ERR_ARG, w + ": null order");
+        else if (strict && !root) rc = fail(RT_ERR_ARG, w + ": null root");
+        else if (strict && (node_slots != 0) != (hnodes != nullptr)) rc = fail(RT_ERR_ARG, w + ": nodes and node_slots disagree");
+        else if (!strict && node_slots && (!hnodes || !root)) rc = fail(RT_ERR_ARG, w + ": null nodes or root");
+        else if ((!strict || node_slots) && n_order && !order) rc = fail(RT_ERR_ARG, w + ": null order");
         else if (node_slots >= (1u << 26) || n_order > (1u << 26)) rc = fail(RT_ERR_ARG, w + ": 2^26 or more node slots or positions");
-        else if (node_slots && (root_word & hrt_winding::LEAF_BIT) == 0u && root_word >= node_slots)
+        else if (!strict && node_slots && (word & hrt_lbvh::LEAF_BIT) == 0u && word >= node_slots)
             rc = fail(RT_ERR_ARG, w + ": the root word names a node past node_slots");
         if (rc) return;
         aee_of_triangles(tris64, n_tris, aee);
+        m = n_tris;
         nodes.resize(2 * node_slots);
         if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
-        if (n_order) ord.assign(order, order + n_order);
-        T.hnodes = nodes.data();
-        T.order = ord.data();
-        T.geo = aee.data();
-        T.m = n_tris;
-        T.root = node_slots ? root_word : hrt_winding::LEAF_BIT;  // (no nodes: the flat definition)
-        if (node_slots) {
-            for (int k = 0; k < 3; k++) T.rc[k] = root[k];
-            T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
+        if ((!strict || node_slots) && n_order) ord.assign(order, order + n_order);
+        if (strict || node_slots) {
+            root_word = word;
+            for (int k = 0; k < 3; k++) rc3[k] = root[k];
+            rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
         }
+    }
+    template <typename T>
+    void fields(T& t) const {
+        t.hnodes = nodes.data();
+        t.order = ord.data();
+        t.geo = aee.data();
+        t.m = m;
+        t.root = root_word;
+        for (int k = 0; k < 3; k++) t.rc[k] = rc3[k];
+        t.rr_h = rr_h;
     }
 };
 }  // namespace
+
+extern "C" {
 
 int rt_winding_numbers(rt_renderer* r, const void* points_dev, uint32_t n, float beta, void* w_dev) {
     if (!r) return fail(RT_ERR_ARG, "rt_winding_numbers: null");
@@ -2237,44 +2300,33 @@ int rt_winding_numbers(rt_renderer* r, const void* points_dev, uint32_t n, float
     if (misaligned(4, {points_dev, w_dev})) return fail(RT_ERR_ARG, "rt_winding_numbers: points and w must be 4-byte aligned");
     if (!hrt_winding::beta_ok(beta))
         return fail(RT_ERR_ARG, "rt_winding_numbers: beta must be 0 (the default 2.0) or at least 1 (+inf: no dipoles)");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_winding_numbers: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_winding_numbers: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
-    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    QueryScope q(r, "rt_winding_numbers");
     if (q.rc) return q.rc;
     if (int rc = ensure_moments(r)) return rc;
     hrt_winding::Launch a{};
-    a.tree.hnodes = (const hrt_winding::U4*)q.P.tb_hnodes;
+    tree_fields(a.tree, q.P);
     a.tree.moments = r->tb_moments.ptr;
-    a.tree.order = q.P.tb_order;
-    a.tree.geo = q.P.tri_geo;
-    a.tree.m = q.P.m;
-    a.tree.root = q.P.tb_root;
-    for (int k = 0; k < 3; k++) a.tree.rc[k] = q.P.tb_rc[k];
-    a.tree.rr_h = q.P.tb_rr_h;
     a.points = (const float*)points_dev;
     a.out = (float*)w_dev;
     a.n = n;
     a.beta = beta;
-    if (r->winding_count) {
-        if (int rc = ensure(r->winding_counts, 5)) return rc;
-        HIP_TRY(hipMemsetAsync(r->winding_counts.ptr, 0, 5 * sizeof(unsigned long long), r->stream));
-        a.counts = r->winding_counts.ptr;
-    }
-    HIP_TRY(hrt_launch_winding(a, r->winding_count, r->stream));
+    if (int rc = r->winding_count.arm(5, r->stream, &a.counts)) return rc;
+    HIP_TRY(hrt_launch_winding(a, r->winding_count.on, r->stream));
     return RT_OK;
 }
 
 // The moments on the host (rt_winding.hpp host_moments): pure CPU, no device.
 int rt_host_tree_moments(const void* tris64, uint32_t n_tris, const void* hnodes, size_t node_slots, const uint32_t* order,
                          size_t n_order, uint32_t root_word, const float root[4], void* moments_out, size_t moment_cap) {
-    HostWindingTree H("rt_host_tree_moments", tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    const HostTree H("rt_host_tree_moments", false, tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
     if (H.rc) return H.rc;
     if (node_slots == 0) return RT_OK;  // a tree without nodes has no records
     if (moment_cap < node_slots) return fail(RT_ERR_ARG, "rt_host_tree_moments: moment_cap is below node_slots");
     if (!moments_out) return fail(RT_ERR_ARG, "rt_host_tree_moments: null output");
+    hrt_winding::Tree T{};
+    H.fields(T);
     std::vector<float> rec(hrt_winding::REC_FLOATS * node_slots);
-    if (!hrt_winding::host_moments(H.T, node_slots, n_order, rec.data()))
+    if (!hrt_winding::host_moments(T, node_slots, n_order, rec.data()))
         return fail(RT_ERR_ARG, "rt_host_tree_moments: the nodes are not a tree over order and the triangles");
     std::memcpy(moments_out, rec.data(), rec.size() * sizeof(float));
     return RT_OK;
@@ -2287,30 +2339,15 @@ int rt_host_winding_numbers(const void* tris64, uint32_t n_tris, const void* hno
     if (!hrt_winding::beta_ok(beta))
         return fail(RT_ERR_ARG, "rt_host_winding_numbers: beta must be 0 (the default 2.0) or at least 1 (+inf: no dipoles)");
     if (n && (!points || !w_out)) return fail(RT_ERR_ARG, "rt_host_winding_numbers: null points or w_out");
-    HostWindingTree H("rt_host_winding_numbers", tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    const HostTree H("rt_host_winding_numbers", false, tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
     if (H.rc) return H.rc;
+    hrt_winding::Tree T{};
+    H.fields(T);
     std::vector<float> rec(hrt_winding::REC_FLOATS * std::max<size_t>(node_slots, 1));
-    if (node_slots && !hrt_winding::host_moments(H.T, node_slots, n_order, rec.data()))
+    if (node_slots && !hrt_winding::host_moments(T, node_slots, n_order, rec.data()))
         return fail(RT_ERR_ARG, "rt_host_winding_numbers: the nodes are not a tree over order and the triangles");
-    H.T.moments = rec.data();
-    hrt_winding::host_winding(H.T, points, n, beta, w_out);
-    return RT_OK;
-}
-
-int rt_testing_set_winding_count(rt_renderer* r, uint32_t on) {
-    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_winding_count: null");
-    r->winding_count = on != 0u;
-    return RT_OK;
-}
-
-int rt_testing_get_winding_counts(rt_renderer* r, uint64_t out[5]) {
-    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_winding_counts: null");
-    for (int k = 0; k < 5; k++) out[k] = 0;
-    if (!r->winding_counts.ptr) return RT_OK;
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    HIP_TRY(hipMemcpyAsync(out, r->winding_counts.ptr, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
+    T.moments = rec.data();
+    hrt_winding::host_winding(T, points, n, beta, w_out);
     return RT_OK;
 }
 
@@ -2322,9 +2359,7 @@ int rt_testing_winding_atan2(const float* y, const float* x, uint32_t n, float* 
 
 int rt_testing_get_tree_moments(rt_renderer* r, void* moments_out, size_t moment_cap, size_t* count) {
     if (!r || !count) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: null");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_testing_get_tree_moments: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_testing_get_tree_moments: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
+    if (int rc = need_tri_tree(r, "rt_testing_get_tree_moments")) return rc;
     DeviceScope ds(r->device);
     if (ds.rc) return ds.rc;
     if (int rc = upload_tri_tree(r)) return rc;  // (a host tree not built yet)
@@ -2351,20 +2386,10 @@ int rt_cast_rays_multi(rt_renderer* r, const void* origins_dev, const void* dirs
     if (misaligned(16, {hits_dev}) || misaligned(4, {origins_dev, dirs_dev, tmax_dev, after_dev, counts_dev}))
         return fail(RT_ERR_ARG, "rt_cast_rays_multi: hits must be 16-byte aligned, every other buffer 4-byte aligned");
     static_assert(sizeof(rt_multi_hit) == 16, "rt_multi_hit: one 16-byte store per record (k_cast_rays_multi)");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_cast_rays_multi: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_cast_rays_multi: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
-    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    QueryScope q(r, "rt_cast_rays_multi");
     if (q.rc) return q.rc;
     hrt_multihit::Launch a{};
-    a.tree.hnodes = (const hrt_multihit::U4*)q.P.tb_hnodes;
-    a.tree.order = q.P.tb_order;
-    a.tree.geo = q.P.tri_geo;
-    a.tree.m = q.P.m;
-    a.tree.root = q.P.tb_root;
-    a.tree.flat = 0u;
-    for (int c = 0; c < 3; c++) a.tree.rc[c] = q.P.tb_rc[c];
-    a.tree.rr_h = q.P.tb_rr_h;
+    tree_fields(a.tree, q.P);
     a.origins = (const float*)origins_dev;
     a.dirs = (const float*)dirs_dev;
     a.tmax = (const float*)tmax_dev;
@@ -2373,12 +2398,8 @@ int rt_cast_rays_multi(rt_renderer* r, const void* origins_dev, const void* dirs
     a.counts = (uint32_t*)counts_dev;
     a.n = n;
     a.k = k;
-    if (r->multihit_count) {
-        if (int rc = ensure(r->multihit_counts, 4)) return rc;
-        HIP_TRY(hipMemsetAsync(r->multihit_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
-        a.stats = r->multihit_counts.ptr;
-    }
-    HIP_TRY(hrt_launch_multihit(a, r->multihit_count, r->stream));
+    if (int rc = r->multihit_count.arm(4, r->stream, &a.stats)) return rc;
+    HIP_TRY(hrt_launch_multihit(a, r->multihit_count.on, r->stream));
     return RT_OK;
 }
 
@@ -2390,28 +2411,12 @@ int rt_host_cast_rays_multi(const void* tris64, uint32_t n_tris, const void* hno
     if (k > RT_MULTI_HIT_MAX_K) return fail(RT_ERR_ARG, std::string(who) + ": k exceeds RT_MULTI_HIT_MAX_K");
     if (k == 0 && !counts) return fail(RT_ERR_ARG, std::string(who) + ": k = 0 needs counts");
     if (n && (!origins || !dirs || (k && !hits16))) return fail(RT_ERR_ARG, std::string(who) + ": null rays or hits");
-    if (n_tris && !tris64) return fail(RT_ERR_ARG, std::string(who) + ": null triangles");
-    if (!root) return fail(RT_ERR_ARG, std::string(who) + ": null root");
-    if ((node_slots != 0) != (hnodes != nullptr)) return fail(RT_ERR_ARG, std::string(who) + ": nodes and node_slots disagree");
-    if (node_slots && n_order && !order) return fail(RT_ERR_ARG, std::string(who) + ": null order");
-    if (node_slots >= (1u << 26) || n_order > (1u << 26))
-        return fail(RT_ERR_ARG, std::string(who) + ": 2^26 or more node slots or positions");
-    std::vector<float> aee;
-    aee_of_triangles(tris64, n_tris, aee);
-    std::vector<hrt_multihit::U4> nodes(2 * node_slots);  // copied: no alignment asked of the caller
-    if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
-    std::vector<uint32_t> ord;
-    if (node_slots && n_order) ord.assign(order, order + n_order);
+    const HostTree H(who, true, tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    if (H.rc) return H.rc;
     hrt_multihit::Tree T{};
-    T.hnodes = nodes.data();
-    T.order = ord.data();
-    T.geo = aee.data();
-    T.m = n_tris;
-    T.root = root_word;
+    H.fields(T);
     T.flat = node_slots ? 0u : 1u;
-    for (int c = 0; c < 3; c++) T.rc[c] = root[c];
-    T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
-    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, ord.size()))
+    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, H.ord.size()))
         return fail(RT_ERR_ARG, std::string(who) + ": the nodes are not a tree over order and the triangles");
     std::vector<hrt_multihit::Hit> after, out((size_t)n * k);
     if (after16 && n) {
@@ -2420,23 +2425,6 @@ int rt_host_cast_rays_multi(const void* tris64, uint32_t n_tris, const void* hno
     }
     hrt_multihit::host_multi(T, origins, dirs, tmax, after16 ? after.data() : nullptr, n, k, out.data(), counts);
     if (!out.empty()) std::memcpy(hits16, out.data(), out.size() * sizeof(hrt_multihit::Hit));
-    return RT_OK;
-}
-
-int rt_testing_set_multihit_count(rt_renderer* r, uint32_t on) {
-    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_multihit_count: null");
-    r->multihit_count = on != 0u;
-    return RT_OK;
-}
-
-int rt_testing_get_multihit_counts(rt_renderer* r, uint64_t out[4]) {
-    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_multihit_counts: null");
-    for (int c = 0; c < 4; c++) out[c] = 0;
-    if (!r->multihit_counts.ptr) return RT_OK;
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    HIP_TRY(hipMemcpyAsync(out, r->multihit_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }
 
@@ -2453,20 +2441,10 @@ int rt_overlap_volumes(rt_renderer* r, uint32_t kind, const void* volumes_dev, c
     if (misaligned(16, {hits_dev}) || misaligned(4, {volumes_dev, after_dev, counts_dev}))
         return fail(RT_ERR_ARG, "rt_overlap_volumes: hits must be 16-byte aligned, every other buffer 4-byte aligned");
     static_assert(sizeof(rt_overlap_hit) == 16, "rt_overlap_hit: one 16-byte store per record (k_overlap)");
-    if (r->mode == RT_MODE_SPHERE) return fail(RT_ERR_ARG, "rt_overlap_volumes: the sphere program has no triangle tree");
-    if (!r->dev_geom && !r->params.tri_bvh)
-        return fail(RT_ERR_STATE, "rt_overlap_volumes: no triangle tree (device geometry or rt_params.tri_bvh = 1 has one)");
-    QueryScope q(r);  // (scene_params: upload_tri_tree builds a host SAH tree that is not built yet)
+    QueryScope q(r, "rt_overlap_volumes");
     if (q.rc) return q.rc;
     hrt_overlap::Launch a{};
-    a.tree.hnodes = (const hrt_overlap::U4*)q.P.tb_hnodes;
-    a.tree.order = q.P.tb_order;
-    a.tree.geo = q.P.tri_geo;
-    a.tree.m = q.P.m;
-    a.tree.root = q.P.tb_root;
-    a.tree.flat = 0u;
-    for (int c = 0; c < 3; c++) a.tree.rc[c] = q.P.tb_rc[c];
-    a.tree.rr_h = q.P.tb_rr_h;
+    tree_fields(a.tree, q.P);
     a.volumes = (const float*)volumes_dev;
     a.after = (const hrt_overlap::Hit*)after_dev;
     a.hits = hits_dev;
@@ -2474,12 +2452,8 @@ int rt_overlap_volumes(rt_renderer* r, uint32_t kind, const void* volumes_dev, c
     a.n = n;
     a.k = k;
     a.kind = kind;
-    if (r->overlap_count) {
-        if (int rc = ensure(r->overlap_counts, 4)) return rc;
-        HIP_TRY(hipMemsetAsync(r->overlap_counts.ptr, 0, 4 * sizeof(unsigned long long), r->stream));
-        a.stats = r->overlap_counts.ptr;
-    }
-    HIP_TRY(hrt_launch_overlap(a, r->overlap_count, r->stream));
+    if (int rc = r->overlap_count.arm(4, r->stream, &a.stats)) return rc;
+    HIP_TRY(hrt_launch_overlap(a, r->overlap_count.on, r->stream));
     return RT_OK;
 }
 
@@ -2492,28 +2466,12 @@ int rt_host_overlap_volumes(const void* tris64, uint32_t n_tris, const void* hno
     if (kind != RT_VOLUME_BOX && kind != RT_VOLUME_BALL) return fail(RT_ERR_ARG, std::string(who) + ": unknown kind");
     if (n && k == 0 && !counts) return fail(RT_ERR_ARG, std::string(who) + ": k = 0 needs counts");
     if (n && (!volumes || (k && !hits16))) return fail(RT_ERR_ARG, std::string(who) + ": null volumes or hits");
-    if (n_tris && !tris64) return fail(RT_ERR_ARG, std::string(who) + ": null triangles");
-    if (!root) return fail(RT_ERR_ARG, std::string(who) + ": null root");
-    if ((node_slots != 0) != (hnodes != nullptr)) return fail(RT_ERR_ARG, std::string(who) + ": nodes and node_slots disagree");
-    if (node_slots && n_order && !order) return fail(RT_ERR_ARG, std::string(who) + ": null order");
-    if (node_slots >= (1u << 26) || n_order > (1u << 26))
-        return fail(RT_ERR_ARG, std::string(who) + ": 2^26 or more node slots or positions");
-    std::vector<float> aee;
-    aee_of_triangles(tris64, n_tris, aee);
-    std::vector<hrt_overlap::U4> nodes(2 * node_slots);  // copied: no alignment asked of the caller
-    if (node_slots) std::memcpy(nodes.data(), hnodes, node_slots * 32u);
-    std::vector<uint32_t> ord;
-    if (node_slots && n_order) ord.assign(order, order + n_order);
+    const HostTree H(who, true, tris64, n_tris, hnodes, node_slots, order, n_order, root_word, root);
+    if (H.rc) return H.rc;
     hrt_overlap::Tree T{};
-    T.hnodes = nodes.data();
-    T.order = ord.data();
-    T.geo = aee.data();
-    T.m = n_tris;
-    T.root = root_word;
+    H.fields(T);
     T.flat = node_slots ? 0u : 1u;
-    for (int c = 0; c < 3; c++) T.rc[c] = root[c];
-    T.rr_h = std::nextafter(root[3] * (1.0f + 0x1p-9f), INFINITY);  // (scene_params: tb_rr_h)
-    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, ord.size()))
+    if (node_slots && !hrt_multihit::host_tree_ok(T, node_slots, H.ord.size()))
         return fail(RT_ERR_ARG, std::string(who) + ": the nodes are not a tree over order and the triangles");
     std::vector<hrt_overlap::Hit> after, out((size_t)n * k);
     if (after16 && n) {
@@ -2522,23 +2480,6 @@ int rt_host_overlap_volumes(const void* tris64, uint32_t n_tris, const void* hno
     }
     hrt_overlap::host_overlap(T, kind, volumes, after16 ? after.data() : nullptr, n, k, out.data(), counts);
     if (!out.empty()) std::memcpy(hits16, out.data(), out.size() * sizeof(hrt_overlap::Hit));
-    return RT_OK;
-}
-
-int rt_testing_set_overlap_count(rt_renderer* r, uint32_t on) {
-    if (!r) return fail(RT_ERR_ARG, "rt_testing_set_overlap_count: null");
-    r->overlap_count = on != 0u;
-    return RT_OK;
-}
-
-int rt_testing_get_overlap_counts(rt_renderer* r, uint64_t out[4]) {
-    if (!r || !out) return fail(RT_ERR_ARG, "rt_testing_get_overlap_counts: null");
-    for (int c = 0; c < 4; c++) out[c] = 0;
-    if (!r->overlap_counts.ptr) return RT_OK;
-    DeviceScope ds(r->device);
-    if (ds.rc) return ds.rc;
-    HIP_TRY(hipMemcpyAsync(out, r->overlap_counts.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
     return RT_OK;
 }
 

@@ -23,45 +23,15 @@
 
 #include "../../include/hrt.h"
 #include "rt_closest.hpp"
+#include "rt_wave_stats.hpp"
 
 using hrt_closest::Launch;
 using hrt_closest::Record;
 using hrt_closest::U4;
 
 constexpr uint32_t CP_WG = 256u;
-constexpr uint32_t CP_LEAF_BIT = 0x80000000u;
 static_assert(hrt_closest::T_MISS == RT_T_MISS, "the shared header's miss value is the public one");
 static_assert(sizeof(rt_closest) == sizeof(Record), "rt_closest is the shared Record");
-
-static __device__ inline float half_lo(uint32_t w) {
-    const uint16_t b = (uint16_t)(w & 0xFFFFu);
-    _Float16 h;
-    __builtin_memcpy(&h, &b, sizeof h);
-    return (float)h;
-}
-static __device__ inline float half_hi(uint32_t w) {
-    const uint16_t b = (uint16_t)(w >> 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &b, sizeof h);
-    return (float)h;
-}
-// One axis of the bound: how far q lies outside [lo, hi], less the pad, not below 0. (lo is never +inf, hi never -inf, q
-// is finite: no NaN; an infinite half on the far side gives -inf, which the max drops.)
-static __device__ inline float axis_gap(uint32_t w, float q, float pad) {
-    const float below = half_lo(w) - q, above = q - half_hi(w);
-    const float g = (below > above ? below : above) - pad;
-    return g > 0.0f ? g : 0.0f;
-}
-static __device__ inline float box_lb2(const U4& c, const float q[3], float pad) {
-    const float gx = axis_gap(c.x, q[0], pad), gy = axis_gap(c.y, q[1], pad), gz = axis_gap(c.z, q[2], pad);
-    return (gx * gx + gy * gy) + gz * gz;
-}
-
-static __device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // COUNT: the test-only counting instantiation (include/hrt_testing.h rt_testing_set_closest_count); the product path
 // launches COUNT = false, which holds none of the counting code.
@@ -85,9 +55,9 @@ __global__ __launch_bounds__(CP_WG) void k_closest_points(const Launch A) {
                 uint32_t node = A.root;
                 int sp = 0;
                 while (true) {
-                    if (!(node & CP_LEAF_BIT)) {
+                    if (!(node & hrt_closest::LEAF_BIT)) {
                         const U4 L = A.hnodes[2 * (size_t)node], R = A.hnodes[2 * (size_t)node + 1];
-                        const float ll = box_lb2(L, q, pad), lr = box_lb2(R, q, pad);
+                        const float ll = hrt_closest::box_lb2(L, q, pad), lr = hrt_closest::box_lb2(R, q, pad);
                         const bool vl = !(ll > best), vr = !(lr > best);
                         if (vl && vr) {
                             const bool lfirst = ll <= lr;
@@ -125,14 +95,7 @@ __global__ __launch_bounds__(CP_WG) void k_closest_points(const Launch A) {
         o[1] = uint4{__float_as_uint(rec.p[2]), __float_as_uint(rec.v), __float_as_uint(rec.w), 0u};
     }
     if constexpr (COUNT) {  // per wave: four sums, one agent-scope add per word (every lane of the wave is here)
-        const unsigned long long s0 = wave_sum(active ? 1ull : 0ull), s1 = wave_sum(tests), s2 = wave_sum(overflow),
-                                 s3 = wave_sum(uncovered);
-        if ((threadIdx.x & 63u) == 0u) {
-            __hip_atomic_fetch_add(&A.counts[0], s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.counts[1], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.counts[2], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.counts[3], s3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        hrt_wave::wave_add<4>(A.counts, {active ? 1ull : 0ull, tests, overflow, uncovered});
     }
 }
 

@@ -20,6 +20,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rt_lbvh.hpp"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define HRT_CLOSEST_FN __host__ __device__ inline
@@ -44,17 +46,10 @@ struct Nearest {
     float d2, v, w;
 };
 
-HRT_CLOSEST_FN bool f32_finite(float x) {
-    uint32_t u;
-    __builtin_memcpy(&u, &x, sizeof u);
-    return (u & 0x7F800000u) != 0x7F800000u;
-}
-HRT_CLOSEST_FN float quiet_nan() {
-    const uint32_t u = 0x7FC00000u;
-    float x;
-    __builtin_memcpy(&x, &u, sizeof x);
-    return x;
-}
+using hrt_lbvh::f32_finite;
+using hrt_lbvh::quiet_nan;
+using U4 = hrt_lbvh::U4;  // half a node: one child's six halves and its word (rt_lbvh.hpp pack_child)
+constexpr uint32_t LEAF_BIT = hrt_lbvh::LEAF_BIT;
 HRT_CLOSEST_FN float dot3(const float a[3], const float b[3]) {
     const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
     return (x + y) + z;
@@ -195,9 +190,21 @@ inline void host_closest(const float* geo, uint32_t m, const float* points, cons
 constexpr float D_MIN = 0x1p-40f, D_MAX = 0x1p60f, PAD = 0x1p-12f;
 constexpr int STACK = 24;  // entries of the walk's stack (TRI_STACK of rt_kernels.hip)
 
-struct U4 {
-    uint32_t x, y, z, w;
-};
+// One axis of the bound: how far q lies outside [lo, hi] (the two halves of w), less the pad, not below 0. (lo is never
+// +inf, hi never -inf, q is finite: no NaN; an infinite half on the far side gives -inf, which the max drops.)
+HRT_CLOSEST_FN float axis_gap(uint32_t w, float q, float pad) {
+    const float below = (float)hrt_lbvh::f16_from_bits((uint16_t)(w & 0xFFFFu)) - q;
+    const float above = q - (float)hrt_lbvh::f16_from_bits((uint16_t)(w >> 16));
+    const float g = (below > above ? below : above) - pad;
+    return g > 0.0f ? g : 0.0f;
+}
+// The lower bound of the squared distance from q (relative to the root centre) to a child's box, taken pad closer: the
+// one definition rt_closest.hip's walk and rt_overlap.hpp's ball walk both cull by.
+HRT_CLOSEST_FN float box_lb2(const U4& c, const float q[3], float pad) {
+    const float gx = axis_gap(c.x, q[0], pad), gy = axis_gap(c.y, q[1], pad), gz = axis_gap(c.z, q[2], pad);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
 struct Launch {
     const U4* hnodes;       // the node array: two U4 per node (rt_lbvh.hpp pack_child)
     const uint32_t* order;  // tb_order: the triangle index of every leaf position

@@ -77,6 +77,7 @@ HRT_LBVH_FN double f64_from_bits(uint64_t u) {
     return x;
 }
 HRT_LBVH_FN bool f32_finite(float x) { return (f32_bits(x) & 0x7F800000u) != 0x7F800000u; }
+HRT_LBVH_FN float quiet_nan() { return f32_from_bits(0x7FC00000u); }
 
 // An unsigned key with the order of the f64 values (no NaN): a < b exactly when f64_key(a) < f64_key(b).
 HRT_LBVH_FN uint64_t f64_key(double x) {

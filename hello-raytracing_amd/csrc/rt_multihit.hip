@@ -17,6 +17,7 @@
 
 #include "../../include/hrt.h"
 #include "rt_multihit.hpp"
+#include "rt_wave_stats.hpp"
 
 using hrt_multihit::Hit;
 using hrt_multihit::Launch;
@@ -25,12 +26,6 @@ constexpr uint32_t MH_WG = 256u;
 static_assert(hrt_multihit::T_MISS == RT_T_MISS, "the shared header's miss value is the public one");
 static_assert(hrt_multihit::MAX_K == RT_MULTI_HIT_MAX_K, "the shared header's capacity is the public one");
 static_assert(sizeof(rt_multi_hit) == sizeof(Hit), "rt_multi_hit is the shared Hit");
-
-static __device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <bool COUNT_ALL, bool STATS>
 __global__ __launch_bounds__(MH_WG) void k_cast_rays_multi(const Launch A) {
@@ -62,14 +57,7 @@ __global__ __launch_bounds__(MH_WG) void k_cast_rays_multi(const Launch A) {
         if constexpr (COUNT_ALL) A.counts[i] = count;
     }
     if constexpr (STATS) {  // per wave: four sums, one agent-scope add per word (every lane of the wave is here)
-        const unsigned long long s0 = wave_sum(active ? 1ull : 0ull), s1 = wave_sum(tally.tri), s2 = wave_sum(tally.box),
-                                 s3 = wave_sum(tally.overflow);
-        if ((threadIdx.x & 63u) == 0u) {
-            __hip_atomic_fetch_add(&A.stats[0], s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[1], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[2], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[3], s3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        hrt_wave::wave_add<4>(A.stats, {active ? 1ull : 0ull, tally.tri, tally.box, tally.overflow});
     }
 }
 

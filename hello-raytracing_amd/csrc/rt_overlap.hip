@@ -20,6 +20,7 @@
 
 #include "../../include/hrt.h"
 #include "rt_overlap.hpp"
+#include "rt_wave_stats.hpp"
 
 using hrt_overlap::Hit;
 using hrt_overlap::Launch;
@@ -29,12 +30,6 @@ static_assert(hrt_overlap::T_MISS == RT_T_MISS, "the shared header's miss value 
 static_assert(hrt_overlap::MAX_K == RT_OVERLAP_MAX_K, "the shared header's capacity is the public one");
 static_assert(hrt_overlap::KIND_BOX == RT_VOLUME_BOX && hrt_overlap::KIND_BALL == RT_VOLUME_BALL, "the kinds are the public ones");
 static_assert(sizeof(rt_overlap_hit) == sizeof(Hit), "rt_overlap_hit is the shared Hit");
-
-static __device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <uint32_t KIND, bool COUNT_ALL, bool STATS>
 __global__ __launch_bounds__(OV_WG) void k_overlap(const Launch A) {
@@ -67,14 +62,7 @@ __global__ __launch_bounds__(OV_WG) void k_overlap(const Launch A) {
         if constexpr (COUNT_ALL) A.counts[i] = count;
     }
     if constexpr (STATS) {  // per wave: four sums, one agent-scope add per word (every lane of the wave is here)
-        const unsigned long long s0 = wave_sum(active ? 1ull : 0ull), s1 = wave_sum(tally.tri), s2 = wave_sum(tally.box),
-                                 s3 = wave_sum(tally.overflow);
-        if ((threadIdx.x & 63u) == 0u) {
-            __hip_atomic_fetch_add(&A.stats[0], s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[1], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[2], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(&A.stats[3], s3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        hrt_wave::wave_add<4>(A.stats, {active ? 1ull : 0ull, tally.tri, tally.box, tally.overflow});
     }
 }
 

@@ -31,7 +31,7 @@
 //   box   every ancestor's decoded fp16 box contains box_j (pack_child rounds outward at every step), and clause 2 is
 //         monotone in the box: a larger box passes wherever a smaller one does. So an accepted triangle's ancestors are all
 //         visited, whatever the order; nothing is culled by the list, which sorts by index.
-//   ball  node_lb2 is rt_closest.hip's axis_gap / box_lb2, the same operations in the same order, with
+//   ball  the bound is rt_closest.hpp's box_lb2, the function rt_closest.hip's walk culls by, with
 //         D = |c - rc| * 1.001 + rr_h and pad = D * 2^-12; for D in [2^-40, 2^60] DESIGN.md §7e ("Culling is exact") gives
 //         lb2 < d2_j for every triangle j under the box. A child is visited unless lb2 > bound (equality visits), the bound
 //         being the cap, or without counts the d2 of the k-th entry once the list is full: an accepted triangle the final
@@ -104,18 +104,6 @@ HRT_OVERLAP_FN bool child_meets(const Query& Q, const U4& ch) {
                          hrt_multihit::half_f32(ch.z & 0xFFFFu)};
     const float hi[3] = {hrt_multihit::half_f32(ch.x >> 16), hrt_multihit::half_f32(ch.y >> 16), hrt_multihit::half_f32(ch.z >> 16)};
     return boxes_meet(Q, lo, hi);
-}
-
-// rt_closest.hip's axis_gap and box_lb2: how far q lies outside [lo, hi] per axis, less the pad, not below 0; the sum of
-// the squares as (x + y) + z.
-HRT_OVERLAP_FN float axis_gap(uint32_t w, float q, float pad) {
-    const float below = hrt_multihit::half_f32(w & 0xFFFFu) - q, above = q - hrt_multihit::half_f32(w >> 16);
-    const float g = (below > above ? below : above) - pad;
-    return g > 0.0f ? g : 0.0f;
-}
-HRT_OVERLAP_FN float node_lb2(const U4& ch, const float q[3], float pad) {
-    const float gx = axis_gap(ch.x, q[0], pad), gy = axis_gap(ch.y, q[1], pad), gz = axis_gap(ch.z, q[2], pad);
-    return (gx * gx + gy * gy) + gz * gz;
 }
 
 // False for a box that has no hits by definition.
@@ -243,7 +231,7 @@ HRT_OVERLAP_FN void query(const Tree& T, const float* vol, bool has_after, float
                 hl = child_meets(Q, lc);
                 hr = child_meets(Q, rc);
             } else {
-                const float ll = node_lb2(lc, Q.q_lo, Q.pad), lr = node_lb2(rc, Q.q_lo, Q.pad);
+                const float ll = hrt_closest::box_lb2(lc, Q.q_lo, Q.pad), lr = hrt_closest::box_lb2(rc, Q.q_lo, Q.pad);
                 hl = !(ll > bound);
                 hr = !(lr > bound);
                 lfirst = ll <= lr;

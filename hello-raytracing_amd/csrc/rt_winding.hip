@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/hrt.h"
+#include "rt_wave_stats.hpp"
 #include "rt_winding.hpp"
 
 using hrt_winding::Launch;
@@ -31,12 +32,6 @@ using hrt_winding::U4;
 
 constexpr uint32_t WN_WG = 256u;
 #define HRT_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-static __device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // COUNT: the test-only counting instantiation (include/hrt_testing.h rt_testing_set_winding_count); the product path
 // launches COUNT = false, which holds none of the counting code.
@@ -51,10 +46,7 @@ __global__ __launch_bounds__(WN_WG) void k_winding(const Launch A) {
         A.out[i] = hrt_winding::query<COUNT>(A.tree, p, A.beta, stack_lds + threadIdx.x, WN_WG, t);
     }
     if constexpr (COUNT) {  // per wave: five sums, one agent-scope add per word (every lane of the wave is here)
-        const unsigned long long s[5] = {wave_sum(active ? 1ull : 0ull), wave_sum(t.tri), wave_sum(t.dip), wave_sum(t.overflow),
-                                         wave_sum(t.uncovered)};
-        if ((threadIdx.x & 63u) == 0u)
-            for (int k = 0; k < 5; k++) __hip_atomic_fetch_add(&A.counts[k], s[k], HRT_RLX_AGENT);
+        hrt_wave::wave_add<5>(A.counts, {active ? 1ull : 0ull, t.tri, t.dip, t.overflow, t.uncovered});
     }
 }
 

@@ -43,6 +43,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rt_lbvh.hpp"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define HRT_WINDING_FN __host__ __device__ inline
@@ -56,29 +58,18 @@ namespace hrt_winding {
 
 constexpr float D_MIN = 0x1p-40f, D_MAX = 0x1p60f;  // rt_closest.hpp's covered range
 constexpr int STACK = 24;
-constexpr uint32_t LEAF_BIT = 0x80000000u, NO_PARENT = 0xFFFFFFFFu;
+constexpr uint32_t LEAF_BIT = hrt_lbvh::LEAF_BIT, NO_PARENT = hrt_lbvh::NO_PARENT;
 constexpr float BETA_DEFAULT = 2.0f;
 constexpr float ATAN2_ERR = 5.5e-7f;
 constexpr double TWO_PI = 6.283185307179586;
 constexpr uint32_t REC_FLOATS = 16;  // one node slot of the moments: per child c[3], N[3], 0, 0
 constexpr uint32_t SUM_WORDS = 8;    // f64 per (node, side) in the climb's scratch: N[3], G[3], s, unused
 
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-HRT_WINDING_FN uint32_t f32_bits(float x) {
-    uint32_t u;
-    __builtin_memcpy(&u, &x, sizeof u);
-    return u;
-}
-HRT_WINDING_FN float f32_from_bits(uint32_t u) {
-    float x;
-    __builtin_memcpy(&x, &u, sizeof x);
-    return x;
-}
-HRT_WINDING_FN bool f32_finite(float x) { return (f32_bits(x) & 0x7F800000u) != 0x7F800000u; }
-HRT_WINDING_FN float quiet_nan() { return f32_from_bits(0x7FC00000u); }
+using U4 = hrt_lbvh::U4;
+using hrt_lbvh::f32_bits;
+using hrt_lbvh::f32_finite;
+using hrt_lbvh::f32_from_bits;
+using hrt_lbvh::quiet_nan;
 HRT_WINDING_FN float dot3(const float a[3], const float b[3]) {
     const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
     return (x + y) + z;

@@ -503,19 +503,94 @@ class Renderer:
 
         return torch.device("cuda", self.device()[0])
 
-    def _rays_on_device(self, who: str, a, what: str):
-        """(N, 3) float32 rays as a contiguous tensor on the renderer's device (numpy arrays are uploaded). who: the
-        calling method, for the messages."""
+    def _f32_on_device(self, who: str, what: str, x, shape: tuple, coerce: bool = False, verb: str = "is"):
+        """A numpy array or tensor as a contiguous float32 tensor of `shape` on the renderer's device (numpy arrays are
+        uploaded). shape: None for an extent that is free (printed as N). coerce: a numpy array of another dtype is
+        converted, not refused. who, what, verb: the calling method and the argument, for the messages."""
         import torch
 
         dev = self._torch_device()
-        if not torch.is_tensor(a):
-            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        if a.dtype != torch.float32 or a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f"{who}: {what} must be (N, 3) float32, got {tuple(a.shape)} {a.dtype}")
-        if a.device != dev:
-            raise ValueError(f"{who}: {what} is on {a.device}, the renderer draws on {dev}")
-        return a.contiguous()
+        if not torch.is_tensor(x):
+            x = np.asarray(x)
+            if not coerce and x.dtype != np.float32:
+                raise ValueError(f"{who}: {what} must be float32, got {x.dtype}")
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        if x.dtype != torch.float32 or x.ndim != len(shape) or any(s not in (None, e) for s, e in zip(shape, x.shape)):
+            want = ", ".join("N" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "")
+            raise ValueError(f"{who}: {what} must be ({want}) float32, got {tuple(x.shape)} {x.dtype}")
+        if x.device != dev:
+            raise ValueError(f"{who}: {what} {verb} on {x.device}, the renderer draws on {dev}")
+        return x.contiguous()
+
+    def _rays_on_device(self, who: str, a, what: str):
+        """(N, 3) float32 rays as a contiguous tensor on the renderer's device. who: the calling method, for the messages."""
+        return self._f32_on_device(who, what, a, (None, 3), coerce=True)
+
+    def _cursor(self, who: str, after, dtype, n: int):
+        """The cursors of a paged query, or None: an (n, 4) int32 tensor on the renderer's device, or n numpy records of
+        `dtype`, as a contiguous tensor there."""
+        import torch
+
+        if after is None:
+            return None
+        dev = self._torch_device()
+        cur = after
+        if not torch.is_tensor(cur):
+            cur = np.ascontiguousarray(cur, dtype=dtype).reshape(-1)
+            cur = torch.from_numpy(cur.view(np.int32).reshape(-1, 4)).to(dev)
+        if cur.dtype != torch.int32 or tuple(cur.shape) != (n, 4):
+            raise ValueError(f"{who}: after must be ({n}, 4) int32 records, got {tuple(cur.shape)} {cur.dtype}")
+        if cur.device != dev:
+            raise ValueError(f"{who}: after is on {cur.device}, the renderer draws on {dev}")
+        return cur.contiguous()
+
+    @staticmethod
+    def _k_counts(who: str, k, kmax: int, counts: bool) -> int:
+        """k of a k-nearest query, checked: 0 .. kmax, and 0 only with counts."""
+        k = int(k)
+        if not 0 <= k <= kmax:
+            raise ValueError(f"{who}: k must be 0 .. {kmax}, got {k}")
+        if k == 0 and not counts:
+            raise ValueError(f"{who}: k = 0 needs counts = True")
+        return k
+
+    def _set_testing_count(self, name: str, on: bool) -> None:
+        check(getattr(lib(), f"rt_testing_set_{name}_count")(self._h, 1 if on else 0), f"testing_set_{name}_count")
+
+    def _testing_counts(self, name: str, words: int) -> np.ndarray:
+        c = (C.c_uint64 * words)()
+        check(getattr(lib(), f"rt_testing_get_{name}_counts")(self._h, c), f"testing_get_{name}_counts")
+        return np.array(list(c), dtype=np.uint64)
+
+    def _ragged_pages(self, cnt, K: int, page):
+        """The paging loop of all_hits and all_overlaps. cnt: the (n,) counts of a counting call; page(rows, cursor): the
+        (len(rows), K, 4) int32 records of one more call over the queries `rows`. Returns (offsets, four columns): the
+        first cnt[i] records of query i at [offsets[i], offsets[i + 1]), columns 0, 2, 3 as float32, 1 as int32."""
+        import torch
+
+        dev = self._torch_device()
+        n = int(cnt.shape[0])
+        cnt = cnt.to(torch.int64)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=offsets[1:])
+        total = int(offsets[-1].item()) if n else 0
+        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        rows = torch.nonzero(cnt > 0).reshape(-1)
+        done = torch.zeros((n,), dtype=torch.int64, device=dev)
+        cursor = None
+        rank = torch.arange(K, device=dev, dtype=torch.int64)
+        while rows.numel():
+            rec = page(rows, cursor)
+            left = (cnt[rows] - done[rows]).clamp(max=K)
+            take = rank[None, :] < left[:, None]
+            dst = (offsets[rows] + done[rows])[:, None] + rank[None, :]
+            out[dst[take]] = rec[take]
+            done[rows] += left
+            more = done[rows] < cnt[rows]
+            cursor = rec[more][:, K - 1, :].contiguous()
+            rows = rows[more]
+        f = out.view(torch.float32)
+        return offsets, f[:, 0].clone(), out[:, 1].clone(), f[:, 2].clone(), f[:, 3].clone()
 
     def _ray_pair(self, who: str, origins, dirs):
         """The rays of one query, checked: (origins, dirs, N), both (N, 3) float32 on the renderer's device."""
@@ -583,24 +658,8 @@ class Renderer:
         import torch
 
         o, d, n = self._ray_pair("occluded", origins, dirs)
-        dev = self._torch_device()
-        t = None
-        if tmax is not None:
-            if isinstance(tmax, (int, float)):
-                t = torch.full((n,), float(tmax), dtype=torch.float32, device=dev)
-            else:
-                t = tmax
-                if not torch.is_tensor(t):
-                    t = np.asarray(t)
-                    if t.dtype != np.float32:
-                        raise ValueError(f"occluded: tmax must be float32, got {t.dtype}")
-                    t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-                if t.dtype != torch.float32 or tuple(t.shape) != (n,):
-                    raise ValueError(f"occluded: tmax must be ({n},) float32, got {tuple(t.shape)} {t.dtype}")
-                if t.device != dev:
-                    raise ValueError(f"occluded: tmax is on {t.device}, the renderer draws on {dev}")
-                t = t.contiguous()
-        out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        t = self._per_ray_f32("occluded", "tmax", tmax, n)
+        out = torch.empty((n,), dtype=torch.uint8, device=self._torch_device())
         self._query("occluded", lib().rt_occluded, _ptr(o), _ptr(d), _ptr(t), n, _ptr(out))
         return out != 0
 
@@ -617,24 +676,8 @@ class Renderer:
         n = int(pts.shape[0])
         if n >= 1 << 32:
             raise ValueError(f"{who}: at most 2^32 - 1 points per call")
-        dev = self._torch_device()
-        cap = None
-        if max_dist2 is not None:
-            if isinstance(max_dist2, (int, float)):
-                cap = torch.full((n,), float(max_dist2), dtype=torch.float32, device=dev)
-            else:
-                cap = max_dist2
-                if not torch.is_tensor(cap):
-                    cap = np.asarray(cap)
-                    if cap.dtype != np.float32:
-                        raise ValueError(f"{who}: max_dist2 must be float32, got {cap.dtype}")
-                    cap = torch.from_numpy(np.ascontiguousarray(cap)).to(dev)
-                if cap.dtype != torch.float32 or tuple(cap.shape) != (n,):
-                    raise ValueError(f"{who}: max_dist2 must be ({n},) float32, got {tuple(cap.shape)} {cap.dtype}")
-                if cap.device != dev:
-                    raise ValueError(f"{who}: max_dist2 is on {cap.device}, the renderer draws on {dev}")
-                cap = cap.contiguous()
-        out = torch.empty((n, CLOSEST_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
+        cap = self._per_ray_f32(who, "max_dist2", max_dist2, n)
+        out = torch.empty((n, CLOSEST_DTYPE.itemsize // 4), dtype=torch.int32, device=self._torch_device())
         self._query(who, lib().rt_closest_points, _ptr(pts), _ptr(cap), n, _ptr(out))
         return out
 
@@ -654,14 +697,12 @@ class Renderer:
     def set_closest_count(self, on: bool) -> None:
         """Test-only: closest_points runs the counting instantiation of its kernel (include/hrt_testing.h
         rt_testing_set_closest_count)."""
-        check(lib().rt_testing_set_closest_count(self._h, 1 if on else 0), "testing_set_closest_count")
+        self._set_testing_count("closest", on)
 
     def closest_counts(self) -> np.ndarray:
         """Test-only: uint64[4] of the last counted closest_points call: queries, point-triangle tests, stack overflows,
         points outside the walk's error bound (include/hrt_testing.h rt_testing_get_closest_counts)."""
-        c = (C.c_uint64 * 4)()
-        check(lib().rt_testing_get_closest_counts(self._h, c), "testing_get_closest_counts")
-        return np.array(list(c), dtype=np.uint64)
+        return self._testing_counts("closest", 4)
 
     def _per_ray_f32(self, who: str, what: str, x, n: int):
         """An optional per-ray float: None, a Python float for every ray, or an (n,) float32 numpy array or tensor on the
@@ -670,19 +711,9 @@ class Renderer:
 
         if x is None:
             return None
-        dev = self._torch_device()
         if isinstance(x, (int, float)):
-            return torch.full((n,), float(x), dtype=torch.float32, device=dev)
-        if not torch.is_tensor(x):
-            x = np.asarray(x)
-            if x.dtype != np.float32:
-                raise ValueError(f"{who}: {what} must be float32, got {x.dtype}")
-            x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        if x.dtype != torch.float32 or tuple(x.shape) != (n,):
-            raise ValueError(f"{who}: {what} must be ({n},) float32, got {tuple(x.shape)} {x.dtype}")
-        if x.device != dev:
-            raise ValueError(f"{who}: {what} is on {x.device}, the renderer draws on {dev}")
-        return x.contiguous()
+            return torch.full((n,), float(x), dtype=torch.float32, device=self._torch_device())
+        return self._f32_on_device(who, what, x, (n,))
 
     def cast_rays_multi_records(self, origins, dirs, k: int, tmax=None, after=None, counts: bool = False):
         """rt_cast_rays_multi, the raw records: an (N, k, 4) int32 tensor on the renderer's device, one 16-byte
@@ -694,23 +725,10 @@ class Renderer:
 
         who = "cast_rays_multi"
         o, d, n = self._ray_pair(who, origins, dirs)
-        k = int(k)
-        if not 0 <= k <= MULTI_HIT_MAX_K:
-            raise ValueError(f"{who}: k must be 0 .. {MULTI_HIT_MAX_K}, got {k}")
-        if k == 0 and not counts:
-            raise ValueError(f"{who}: k = 0 needs counts = True")
+        k = self._k_counts(who, k, MULTI_HIT_MAX_K, counts)
         dev = self._torch_device()
         cap = self._per_ray_f32(who, "tmax", tmax, n)
-        cur = after
-        if cur is not None:
-            if not torch.is_tensor(cur):
-                cur = np.ascontiguousarray(cur, dtype=MULTI_HIT_DTYPE).reshape(-1)
-                cur = torch.from_numpy(cur.view(np.int32).reshape(-1, 4)).to(dev)
-            if cur.dtype != torch.int32 or tuple(cur.shape) != (n, 4):
-                raise ValueError(f"{who}: after must be ({n}, 4) int32 records, got {tuple(cur.shape)} {cur.dtype}")
-            if cur.device != dev:
-                raise ValueError(f"{who}: after is on {cur.device}, the renderer draws on {dev}")
-            cur = cur.contiguous()
+        cur = self._cursor(who, after, MULTI_HIT_DTYPE, n)
         hits = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
         cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
         self._query(who, lib().rt_cast_rays_multi, _ptr(o), _ptr(d), _ptr(cap), _ptr(cur), n, k, _ptr(hits) if k else None,
@@ -739,47 +757,23 @@ class Renderer:
         """Every hit of every ray, ragged: one counting call (k = 0), then pages of 16 by cursor over the rays that still
         have hits left. Returns (offsets, t, prim, u, v) on the renderer's device: offsets (N + 1,) int64, ray i's hits at
         [offsets[i], offsets[i + 1]) of t (float32), prim (int32), u, v (float32), in (t, prim) order."""
-        import torch
-
         who = "all_hits"
         o, d, n = self._ray_pair(who, origins, dirs)
-        dev = self._torch_device()
         cap = self._per_ray_f32(who, "tmax", tmax, n)
         _, cnt = self.cast_rays_multi_records(o, d, 0, cap, None, True)
-        cnt = cnt.to(torch.int64)
-        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
-        torch.cumsum(cnt, 0, out=offsets[1:])
-        total = int(offsets[-1].item()) if n else 0
-        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
-        rays = torch.nonzero(cnt > 0).reshape(-1)
-        done = torch.zeros((n,), dtype=torch.int64, device=dev)
-        cursor = None
         K = MULTI_HIT_MAX_K
-        rank = torch.arange(K, device=dev, dtype=torch.int64)
-        while rays.numel():
-            rec, _ = self.cast_rays_multi_records(o[rays], d[rays], K, None if cap is None else cap[rays], cursor, False)
-            left = (cnt[rays] - done[rays]).clamp(max=K)
-            take = rank[None, :] < left[:, None]
-            dst = (offsets[rays] + done[rays])[:, None] + rank[None, :]
-            out[dst[take]] = rec[take]
-            done[rays] += left
-            more = done[rays] < cnt[rays]
-            cursor = rec[more][:, K - 1, :].contiguous()
-            rays = rays[more]
-        f = out.view(torch.float32)
-        return offsets, f[:, 0].clone(), out[:, 1].clone(), f[:, 2].clone(), f[:, 3].clone()
+        return self._ragged_pages(cnt, K, lambda rays, cursor: self.cast_rays_multi_records(
+            o[rays], d[rays], K, None if cap is None else cap[rays], cursor, False)[0])
 
     def set_multihit_count(self, on: bool) -> None:
         """Test-only: cast_rays_multi runs the counting instantiation of its kernel (include/hrt_testing.h
         rt_testing_set_multihit_count)."""
-        check(lib().rt_testing_set_multihit_count(self._h, 1 if on else 0), "testing_set_multihit_count")
+        self._set_testing_count("multihit", on)
 
     def multihit_counts(self) -> np.ndarray:
         """Test-only: uint64[4] of the last counted cast_rays_multi call: queries, triangle tests, box tests, stack
         overflows (include/hrt_testing.h rt_testing_get_multihit_counts)."""
-        c = (C.c_uint64 * 4)()
-        check(lib().rt_testing_get_multihit_counts(self._h, c), "testing_get_multihit_counts")
-        return np.array(list(c), dtype=np.uint64)
+        return self._testing_counts("multihit", 4)
 
     def overlap_records(self, kind: int, volumes, k: int, after=None, counts: bool = False):
         """rt_overlap_volumes, the raw records: an (N, k, 4) int32 tensor on the renderer's device, one 16-byte
@@ -795,35 +789,12 @@ class Renderer:
             raise ValueError(f"{who}: kind must be VOLUME_BOX or VOLUME_BALL, got {kind}")
         width = _VOLUME_FLOATS[kind]
         dev = self._torch_device()
-        vol = volumes
-        if not torch.is_tensor(vol):
-            vol = np.asarray(vol)
-            if vol.dtype != np.float32:
-                raise ValueError(f"{who}: volumes must be float32, got {vol.dtype}")
-            vol = torch.from_numpy(np.ascontiguousarray(vol)).to(dev)
-        if vol.dtype != torch.float32 or vol.dim() != 2 or vol.shape[1] != width:
-            raise ValueError(f"{who}: volumes must be (N, {width}) float32, got {tuple(vol.shape)} {vol.dtype}")
-        if vol.device != dev:
-            raise ValueError(f"{who}: volumes are on {vol.device}, the renderer draws on {dev}")
-        vol = vol.contiguous()
+        vol = self._f32_on_device(who, "volumes", volumes, (None, width), verb="are")
         n = int(vol.shape[0])
         if n >= 1 << 32:
             raise ValueError(f"{who}: at most 2^32 - 1 queries per call")
-        k = int(k)
-        if not 0 <= k <= OVERLAP_MAX_K:
-            raise ValueError(f"{who}: k must be 0 .. {OVERLAP_MAX_K}, got {k}")
-        if k == 0 and not counts:
-            raise ValueError(f"{who}: k = 0 needs counts = True")
-        cur = after
-        if cur is not None:
-            if not torch.is_tensor(cur):
-                cur = np.ascontiguousarray(cur, dtype=OVERLAP_HIT_DTYPE).reshape(-1)
-                cur = torch.from_numpy(cur.view(np.int32).reshape(-1, 4)).to(dev)
-            if cur.dtype != torch.int32 or tuple(cur.shape) != (n, 4):
-                raise ValueError(f"{who}: after must be ({n}, 4) int32 records, got {tuple(cur.shape)} {cur.dtype}")
-            if cur.device != dev:
-                raise ValueError(f"{who}: after is on {cur.device}, the renderer draws on {dev}")
-            cur = cur.contiguous()
+        k = self._k_counts(who, k, OVERLAP_MAX_K, counts)
+        cur = self._cursor(who, after, OVERLAP_HIT_DTYPE, n)
         hits = torch.empty((n, k, 4), dtype=torch.int32, device=dev)
         cnt = torch.empty((n,), dtype=torch.int32, device=dev) if counts else None
         self._query(who, lib().rt_overlap_volumes, kind, _ptr(vol), _ptr(cur), n, k, _ptr(hits) if k else None, _ptr(cnt))
@@ -884,41 +855,18 @@ class Renderer:
         dev = self._torch_device()
         vol = volumes if torch.is_tensor(volumes) else torch.from_numpy(np.ascontiguousarray(volumes)).to(dev)
         _, cnt = self.overlap_records(kind, vol, 0, None, True)
-        n = int(vol.shape[0])
-        cnt = cnt.to(torch.int64)
-        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
-        torch.cumsum(cnt, 0, out=offsets[1:])
-        total = int(offsets[-1].item()) if n else 0
-        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
-        rows = torch.nonzero(cnt > 0).reshape(-1)
-        done = torch.zeros((n,), dtype=torch.int64, device=dev)
-        cursor = None
         K = OVERLAP_MAX_K
-        rank = torch.arange(K, device=dev, dtype=torch.int64)
-        while rows.numel():
-            rec, _ = self.overlap_records(kind, vol[rows], K, cursor, False)
-            left = (cnt[rows] - done[rows]).clamp(max=K)
-            take = rank[None, :] < left[:, None]
-            dst = (offsets[rows] + done[rows])[:, None] + rank[None, :]
-            out[dst[take]] = rec[take]
-            done[rows] += left
-            more = done[rows] < cnt[rows]
-            cursor = rec[more][:, K - 1, :].contiguous()
-            rows = rows[more]
-        f = out.view(torch.float32)
-        return offsets, f[:, 0].clone(), out[:, 1].clone(), f[:, 2].clone(), f[:, 3].clone()
+        return self._ragged_pages(cnt, K, lambda rows, cursor: self.overlap_records(kind, vol[rows], K, cursor, False)[0])
 
     def set_overlap_count(self, on: bool) -> None:
         """Test-only: overlap_records runs the counting instantiation of its kernel (include/hrt_testing.h
         rt_testing_set_overlap_count)."""
-        check(lib().rt_testing_set_overlap_count(self._h, 1 if on else 0), "testing_set_overlap_count")
+        self._set_testing_count("overlap", on)
 
     def overlap_counts(self) -> np.ndarray:
         """Test-only: uint64[4] of the last counted overlap_records call: queries, triangle tests, box tests, stack
         overflows (include/hrt_testing.h rt_testing_get_overlap_counts)."""
-        c = (C.c_uint64 * 4)()
-        check(lib().rt_testing_get_overlap_counts(self._h, c), "testing_get_overlap_counts")
-        return np.array(list(c), dtype=np.uint64)
+        return self._testing_counts("overlap", 4)
 
     def winding_numbers(self, points, beta: float = 0.0):
         """rt_winding_numbers: the generalized winding number of the renderer's triangles at each point (triangle and
@@ -954,14 +902,12 @@ class Renderer:
     def set_winding_count(self, on: bool) -> None:
         """Test-only: winding_numbers runs the counting instantiation of its kernel (include/hrt_testing.h
         rt_testing_set_winding_count)."""
-        check(lib().rt_testing_set_winding_count(self._h, 1 if on else 0), "testing_set_winding_count")
+        self._set_testing_count("winding", on)
 
     def winding_counts(self) -> np.ndarray:
         """Test-only: uint64[5] of the last counted winding_numbers call: queries, triangle terms, dipole terms, stack
         overflows, uncovered points (include/hrt_testing.h rt_testing_get_winding_counts)."""
-        c = (C.c_uint64 * 5)()
-        check(lib().rt_testing_get_winding_counts(self._h, c), "testing_get_winding_counts")
-        return np.array(list(c), dtype=np.uint64)
+        return self._testing_counts("winding", 5)
 
     def tree_moments(self) -> np.ndarray:
         """Test-only (include/hrt_testing.h rt_testing_get_tree_moments): the moments winding_numbers reads, (node slots,
@@ -1300,18 +1246,18 @@ def closest_points_host(triangles: np.ndarray, points: np.ndarray, max_dist2=Non
     return out
 
 
-def _winding_tree_args(triangles, tree):
-    """(triangles, m, nodes, slots, order, n_order, root word, root) as the two host calls take them; tree: a dict of
-    lbvh_build / lbvh_refit / Renderer.tri_tree, or None for the flat definition."""
+def _tree_args(triangles, tree, flat: bool = False):
+    """(triangles, m, nodes, slots, order, n_order, root word, root) as the host mirrors take them; tree: a dict of
+    lbvh_build / lbvh_refit / Renderer.tri_tree, or None for the flat definition without a root. flat: the flat definition
+    with the tree's root (centre, radius): no nodes, no order, a leaf root word."""
     t = _triangle_records(triangles)
     m = len(t)
-    if tree is None:
-        nodes, order = np.zeros((0, 8), dtype=np.uint32), np.zeros((0,), dtype=np.uint32)
-        word, root = 0x80000000, np.zeros((4,), dtype=np.float32)
-    else:
+    nodes, order, word = np.zeros((0, 8), dtype=np.uint32), np.zeros((0,), dtype=np.uint32), 0x80000000
+    root = np.zeros((4,), dtype=np.float32) if tree is None else np.ascontiguousarray(tree["root"], dtype=np.float32)
+    if tree is not None and not flat:
         nodes = np.ascontiguousarray(tree["nodes"], dtype=np.uint32).reshape(-1, 8)
         order = np.ascontiguousarray(tree["order"], dtype=np.uint32)
-        word, root = int(tree["info"][3]), np.ascontiguousarray(tree["root"], dtype=np.float32)
+        word = int(tree["info"][3])
     keep = (t, nodes, order, root)
     return keep, (t.ctypes.data if m else None, m, nodes.ctypes.data if len(nodes) else None, len(nodes),
                   order.ctypes.data_as(_lib._PU32) if len(order) else None, len(order), word, root.ctypes.data_as(_lib._PF))
@@ -1320,7 +1266,7 @@ def _winding_tree_args(triangles, tree):
 def tree_moments_host(triangles: np.ndarray, tree: dict) -> np.ndarray:
     """rt_host_tree_moments (include/hrt.h): the moments of a tree dict's subtrees on the host, no device: (node slots, 16)
     float32, per child c xyz (relative to the root centre), N xyz, 0, 0. A tree without nodes gives no records."""
-    keep, args = _winding_tree_args(triangles, tree)
+    keep, args = _tree_args(triangles, tree)
     out = np.zeros((len(keep[1]), 16), dtype=np.float32)
     check(lib().rt_host_tree_moments(*args, out.ctypes.data if out.size else None, len(out)), "rt_host_tree_moments")
     return out
@@ -1330,7 +1276,7 @@ def winding_numbers_host(triangles: np.ndarray, tree, points: np.ndarray, beta: 
     """rt_host_winding_numbers (include/hrt.h): Renderer.winding_numbers on the host, no device, for the tree dict `tree`
     (the bytes the device writes for that tree), or the flat definition — every triangle, no dipoles — with tree = None.
     Returns (n,) float32."""
-    keep, args = _winding_tree_args(triangles, tree)
+    keep, args = _tree_args(triangles, tree)
     p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
     n = len(p)
     out = np.zeros((n,), dtype=np.float32)
@@ -1347,9 +1293,7 @@ def cast_rays_multi_host(triangles: np.ndarray, tree: dict, origins: np.ndarray,
     tmax: None, a float for every ray, or (n,) float32; after: None or n MULTI_HIT_DTYPE records (t and prim are read).
     Returns (n, k) MULTI_HIT_DTYPE records, and with counts = True a pair of them and (n,) uint32 counts (k = 0 needs
     counts)."""
-    keep, args = _winding_tree_args(triangles, tree)
-    if flat:
-        args = args[:2] + (None, 0, None, 0, 0x80000000) + args[7:]
+    keep, args = _tree_args(triangles, tree, flat)
     o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
     d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
     n = len(o)
@@ -1386,9 +1330,7 @@ def overlap_volumes_host(triangles: np.ndarray, tree: dict, kind: int, volumes: 
     kind: VOLUME_BOX (volumes (n, 6) float32) or VOLUME_BALL ((n, 4) float32); after: None or n OVERLAP_HIT_DTYPE records
     (d2 and prim are read). Returns (n, k) OVERLAP_HIT_DTYPE records, and with counts = True a pair of them and (n,)
     uint32 counts (k = 0 needs counts)."""
-    keep, args = _winding_tree_args(triangles, tree)
-    if flat:
-        args = args[:2] + (None, 0, None, 0, 0x80000000) + args[7:]
+    keep, args = _tree_args(triangles, tree, flat)
     width = _VOLUME_FLOATS.get(kind, 1)
     vol = np.ascontiguousarray(volumes, dtype=np.float32).reshape(-1, width)
     n = len(vol)

@@ -3,7 +3,8 @@
 // finite, NaN and infinite points, every class of cap. Checks what must hold for every input: v >= 0, w >= 0, v + w <= 1,
 // a d2 that is never NaN in a record, a miss record that is all zeros below prim. Exit status 0 and "clean".
 //
-//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+// (clang++: rt_closest.hpp includes rt_lbvh.hpp, which uses _Float16; g++ has it from version 12 on)
+//   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -I hello-raytracing_amd/csrc scripts/closest_sanitize.cpp -o /tmp/closest_sanitize && /tmp/closest_sanitize
 #include <cmath>
 #include <cstdio>

@@ -16,6 +16,9 @@ HERE = Path(__file__).resolve().parent
 LIB = HERE / "build" / "liboracle.so"
 
 MODE_SPHERE, MODE_TRIS, MODE_MIXED = 0, 1, 2
+# step_cap of the walks that are not the reference's (tri_bvh = 1, the device trees): no cap, and a ray with a NaN or
+# infinite component takes the triangle test over every triangle in index order (rt_oracle.c STEP_CAP_SAH, include/hrt.h)
+STEP_CAP_SAH = 0xFFFFFFFF
 
 
 class OParams(C.Structure):
@@ -198,7 +201,7 @@ def render(*, width: int, height: int, mode: int, camera: np.ndarray, frames: in
     rows: (row0, row_step, nrows[, row_block]) subset of rows (global coordinates), default all rows; with
     row_block b > 1 local row k is row0 + (k // b) * row_step * b + k % b (rt_params.row_block).
     step_cap: the reference walk's 600-step cap (shader_tris.wgsl:274); 0 = uncapped (only to check the
-    opt-in SAH triangle walk, which has no cap).
+    opt-in SAH triangle walk, which has no cap); STEP_CAP_SAH = uncapped, with that walk's rule for non-finite rays.
     Returns (image[nrows, nx, 3] float32, queries).
     """
     if bounces is None:

@@ -263,7 +263,17 @@ static inline void tri_test(const o_scene *sc, ray_t r, uint32_t j, hit_t *h) {
 }
 
 /* intersect_all_node: shader_tris.wgsl:268-301 — stackless walk of the implicit heap, 600-step cap */
+/* step_cap STEP_CAP_SAH: no cap, and the contract of the walks that are not the reference's (tri_bvh = 1 and the device
+ * trees, include/hrt.h): a ray with a NaN or infinite component is answered by tri_test over every triangle in index order,
+ * as if the heap walk reached every leaf; no box is tested for it. (A ray that is all NaN fails the root box in the heap
+ * walk and misses; under this rule every triangle gives it a NaN t, which `t < EPSILON || t >= hit.t` accepts.) */
+#define STEP_CAP_SAH 0xFFFFFFFFu
 static void closest_bvh(const o_scene *sc, ray_t r, hit_t *h, uint64_t *cnt) {
+    if (sc->step_cap == STEP_CAP_SAH && !(isfinite(r.o.x) && isfinite(r.o.y) && isfinite(r.o.z) && isfinite(r.d.x) &&
+                                          isfinite(r.d.y) && isfinite(r.d.z))) {
+        for (uint32_t j = 0; j < sc->m; j++) { cnt[2]++; tri_test(sc, r, j, h); }
+        return;
+    }
     v3 inv = V(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
     uint32_t i = 1, n = sc->n, m = sc->m;
     const uint32_t cap = sc->step_cap ? sc->step_cap : 0xFFFFFFFFu;

@@ -8,10 +8,7 @@ kernels the draws report (rt_stats.kernel) must equal the set in the code object
 no default or test path reaches), and each draw must match the oracle bit for bit with its ray count (the opt-in SAH
 walk, non-parity by contract, against the uncapped oracle).
 """
-import re
 import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -19,10 +16,9 @@ import pytest
 import hrt
 import scenes
 from hrt import PI, Camera, Vec3, f32
+from kernel_cases import library_kernels, param_cases
 
 pytestmark = pytest.mark.gpu
-
-LIB = Path(__file__).resolve().parents[1] / "hello-raytracing_amd" / "lib" / "libhrt.so"
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,50 +27,25 @@ def _need_gpu():
         pytest.fail("no GPU visible: -m gpu tests must run on an MI355X box (there is no CPU fallback)")
 
 
-def library_kernels() -> set:
-    """Demangled names of the ray-tracing kernels in the code object (their kernel-descriptor symbols)."""
-    data = LIB.read_bytes()
-    syms = sorted({m.decode() for m in re.findall(rb"_Z[0-9A-Za-z_]*k_(?:trace|render)[0-9A-Za-z_]*\.kd", data)})
-    out = subprocess.run(["c++filt"], input="\n".join(s[:-3] for s in syms), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return {re.sub(r"^void ", "", s.split("(")[0]) for s in out if s.strip()}
-
-
 def _deep_spheres():
     """Two seeded cover scenes: a culling BVH of > 192 nodes (k_trace_split without LDS nodes)."""
     return np.concatenate([scenes.rtiow_spheres(42), scenes.rtiow_spheres(7)])
 
 
 def _cases():
-    c3 = scenes.config_c3(40, 24, 3)
+    """kernel_cases.param_cases() on the demo scenes of each role."""
     deep = scenes.config_c3(40, 24, 3)
     deep.spheres = _deep_spheres()
-    c4 = scenes.config_c4(40, 24, 3)  # 1 sphere: the simple scan
     defer = scenes.config_c4(40, 24, 3)
     defer.spheres = np.concatenate([defer.spheres, scenes.rtiow_spheres()[1:12]])  # 12 slots: the deferred scan
     bvh = scenes.config_c4(40, 24, 3)
     bvh.spheres = np.concatenate([bvh.spheres, scenes.rtiow_spheres()[1:60]])  # 60 slots: the culling BVH
     suz = hrt.SceneTris.new_suzane(40, 24)
     tris = scenes.SceneDef("suzane", hrt.RT_MODE_TRIS, 40, 24, suz.camera, bvh=suz.tris_bvh.view(), frames=3)
-    Q, T = hrt.RT_SCHEDULE_QUEUE, hrt.RT_SCHEDULE_TILES
-    cases = []
-    for sd in (c3, deep):
-        for steal in (1, 2):
-            for count in (0, 1):
-                for packet in ((1, 2) if sd is c3 else (0,)):  # (the packet walk needs the LDS nodes: not the deep tree)
-                    cases.append((sd, dict(schedule=Q, steal=steal, count_tests=count, packet=packet)))
-    for v in (1, 3):
-        cases.append((c3, dict(schedule=Q, variant=v, steal=1)))
-    for v in (1, 3, 4):
-        cases.append((c3, dict(schedule=T, variant=v)))
-    for sd in (tris, c4, defer, bvh):
-        for heap_lds in (1, 2):
-            for steal in (1, 2):
-                cases.append((sd, dict(schedule=Q, heap_lds=heap_lds, steal=steal)))
-        for tri_bvh in (0, 1):
-            cases.append((sd, dict(schedule=T, tri_bvh=tri_bvh)))
-        cases.append((sd, dict(schedule=Q, tri_bvh=1)))
-    return cases
+    by_role = {"c3": scenes.config_c3(40, 24, 3), "deep": deep, "tris": tris,
+               "c4": scenes.config_c4(40, 24, 3),  # 1 sphere: the simple scan
+               "defer": defer, "bvh": bvh}
+    return [(by_role[role], params) for role, params in param_cases()]
 
 
 def test_every_instantiation_is_reached():
